@@ -4,15 +4,21 @@
 One step = decompress every block of the rank's shard once (1 M x 16 KiB text-like
 blocks by default, ~2x compressible), inputs already resident in HBM.  Blocks are
 generated on the GPU (deterministic text) and compressed on the GPU
-by this library's encoder; the round trip is verified on device before timing.
+by this library's encoder; with --full the round trip is verified on device before timing.
 
 Multi-GPU: one process per GPU (torch.distributed.run); each rank owns an
 independent shard of blocks (weak scaling, no data-path collective); timing is
 barrier + synchronize bracketed and max-reduced over ranks.
 
-Prints one JSON line (rank 0).  See DESIGN.md §3 for the roofline accounting.  The default c2
-run (1 M x 16 KiB) also measures BASELINE config c3 -- compress + fused CRC32 of 1 M x 64 KiB
-image-like values, the "(+compress)" of the metric -- after releasing the c2 buffers, and reports
+Prints one JSON line (rank 0).  See DESIGN.md §3 for the roofline accounting.
+
+A plain run does only what the headline figure needs: it generates and compresses the shard,
+warms up, times --steps steps, checks the status of the last step, writes that step's outputs
+when --dump-outputs DIR is given (DIR/<name>.npy, see dump_outputs) and prints the line.  Every
+other measurement and check is behind --full: the device round trip against the regenerated
+blocks before timing, the CPU baselines and their sampled bit-exactness check, the "crc" leg and
+the legs below.  With --full the default c2 run (1 M x 16 KiB) also measures BASELINE config c3
+-- compress + fused CRC32 of 1 M x 64 KiB image-like values, the "(+compress)" of the metric -- after releasing the c2 buffers, and reports
 it under "compress" in the same line (--no-c3 skips it; --config c3 runs it alone); then config c4
 -- .data replay of one ~50 GiB corpus of chunk files split over the ranks on record boundaries,
 device-resident and pipelined end to end -- under "replay" (--no-c4 skips it); then config c5
@@ -54,8 +60,15 @@ def parse():
     p.add_argument("--standin", choices=["cpu"], default=None,
                    help="launcher test only: a CPU stand-in step on gloo instead of the GPU codec "
                         "(no measurement; used by tests/test_bench_launcher.py)")
-    p.add_argument("--steps", type=int, default=10)
+    p.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the device round trip check before "
+                        "timing, the CPU baselines, the \"crc\" leg and the c3 / c4 / record-encode / c5 legs "
+                        "(the --no-* options below pick among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step returned to DIR/<name>.npy "
+                        "(c2 and c3; a fixed seeded sample of the blocks' bytes, see dump_outputs)")
     p.add_argument("--blocks", type=int, default=1 << 20, help="blocks per GPU")
     p.add_argument("--block-size", type=int, default=None,
                    help="bytes per block (default: 16384; 65536 for --config c3 / --mode compress)")
@@ -86,7 +99,12 @@ def parse():
     p.add_argument("--traffic-json", default=None,
                    help="PMC HBM bytes per block (tools/traffic.py output); default: the committed "
                         "profiles/r05_c2_traffic.json for the c2 workload")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and (args.standin or args.config == "c5"):
+        p.error("--dump-outputs covers the c2 and c3 workloads")
+    return args
 
 
 def launch(n: int, argv: list[str]) -> int:
@@ -177,17 +195,18 @@ def main():
     dsum = n * bs
     log(f"compressed {csum / 2**30:.2f} GiB, ratio {csum / dsum:.3f}")
 
-    # ---- correctness gate on device: decompress once and compare ----
-    dsz, st, _ = batch.decompress(src, out, max_dsize=bs, workspace=ws)
-    torch.cuda.synchronize()
-    assert int((st != 0).sum().item()) == 0, "decompress status"
-    for c0 in range(0, uniq, args.gen_chunk):   # every unique block, chunk by chunk
-        m = min(args.gen_chunk, uniq - c0)
-        check = batch.synth(kind, 0x5EED2026, [bs] * m, first_id=first + c0, device=dev)
-        if not torch.equal(out.data[c0 * bs:(c0 + m) * bs], check.data[:m * bs]):
-            raise SystemExit(f"round trip mismatch in blocks {c0}..{c0 + m}")
-        del check
-    log("device round trip verified")
+    if args.full:
+        # ---- correctness gate on device: decompress once and compare ----
+        dsz, st, _ = batch.decompress(src, out, max_dsize=bs, workspace=ws)
+        torch.cuda.synchronize()
+        assert int((st != 0).sum().item()) == 0, "decompress status"
+        for c0 in range(0, uniq, args.gen_chunk):   # every unique block, chunk by chunk
+            m = min(args.gen_chunk, uniq - c0)
+            check = batch.synth(kind, 0x5EED2026, [bs] * m, first_id=first + c0, device=dev)
+            if not torch.equal(out.data[c0 * bs:(c0 + m) * bs], check.data[:m * bs]):
+                raise SystemExit(f"round trip mismatch in blocks {c0}..{c0 + m}")
+            del check
+        log("device round trip verified")
 
     crc_state = crc_expect = None
     if args.crc:
@@ -196,10 +215,11 @@ def main():
 
     # ---- timed region ----
     stream = torch.cuda.current_stream()
+    last = [None]   # what the latest step returned: (dsize, status, crc_out)
 
     def step():
-        batch.decompress(src, out, crc_state=crc_state, crc_expect=crc_expect, max_dsize=bs,
-                         workspace=ws, stream=stream)
+        last[0] = batch.decompress(src, out, crc_state=crc_state, crc_expect=crc_expect, max_dsize=bs,
+                                   workspace=ws, stream=stream)
 
     for _ in range(args.warmup):
         step()
@@ -223,8 +243,21 @@ def main():
     tot = shard.sum_over_ranks({"out_bytes": dsum, "in_bytes": csum}, device=dev)
     ms_per_step = wall * 1e3 / args.steps
 
+    dsz, st, _ = last[0]
+    if int((st != 0).sum().item()):
+        raise SystemExit("decompress status of the last timed step")
+    if args.dump_outputs:
+        # what a caller of the timed call holds after the last step: the decoded blocks (dst), their
+        # sizes and statuses; "out_crc32" digests every decoded block, the byte sample shows some whole
+        dump_outputs(args.dump_outputs, rank, {
+            "out": sample_rows(out.data, out.off, dsz, bs),
+            "out_crc32": block_array(batch.crc32(batch.BlockBatch(out.data, out.off, dsz)), unsigned=True),
+            "dsize": block_array(dsz), "status": block_array(st)})
+    last[0] = None
+    del dsz, st
+
     crc_leg = None
-    if not args.crc and not args.no_crc_leg:
+    if args.full and not args.crc and not args.no_crc_leg:
         # the read path always verifies the record CRC (store/datafile.go:161-168): the same shard
         # decoded with the CRC fused into the pass and checked against the stored values' CRCs
         cst = torch.full((n,), -1, dtype=torch.int32, device=dev)
@@ -274,7 +307,7 @@ def main():
                            f"(PMC, committed) x {n} blocks")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:  # the CPU leg: rank 0 at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:  # the CPU leg: rank 0 at N = 1 only
         # the first 256 GPU-compressed blocks of rank 0 = blocks 0..255 of the CPU leg's sample
         ns = min(256, uniq)
         cb = cbuf[: int(coff[ns - 1]) + int(cs_all[ns - 1])].cpu().numpy()
@@ -308,7 +341,8 @@ def main():
         if crc_leg is not None:
             rec["crc"] = crc_leg
     comp = None
-    legs = args.mode == "decompress" and args.block_size == 16384 and (args.blocks == 1 << 20 or args.legs_small)
+    legs = (args.full and args.mode == "decompress" and args.block_size == 16384
+            and (args.blocks == 1 << 20 or args.legs_small))
     if not args.no_c3 and legs:
         # BASELINE config c3 (the "+compress" of the metric) in the same driver run: the c2 buffers
         # are released first; value/roofline/cpu_baseline of c3 go under "compress"
@@ -317,7 +351,7 @@ def main():
         torch.cuda.empty_cache()
         a3 = argparse.Namespace(**vars(args))
         a3.mode, a3.block_size, a3.steps, a3.warmup = "compress", 65536, args.c3_steps, 1
-        a3.traffic_json = None
+        a3.traffic_json = a3.dump_outputs = None
         comp = bench_compress(a3, rank, world, dev, "image", emit=False)
     replay_rec = None
     if not args.no_c4 and legs:
@@ -371,6 +405,45 @@ def main():
 
 
 SEED = 0x5EED2026
+
+# --dump-outputs: at most 1 Mi entries of a per-block array and 8 Mi sampled block bytes are written
+# (float32 / float64: under 51 MB for the four arrays of a run)
+DUMP_BLOCKS = 1 << 20
+DUMP_BYTES = 8 << 20
+
+
+def _pick(n: int, k: int) -> np.ndarray:
+    """Every index below n when n <= k, else a fixed (seeded) sorted sample of k of them."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(n, k, replace=False)).astype(np.int64)
+
+
+def block_array(t: torch.Tensor, unsigned: bool = False) -> np.ndarray:
+    """A per-block int32 device array as float32 (sizes, statuses: exact below 2^24) or, read as
+    uint32 (CRCs), float64; arrays over DUMP_BLOCKS entries are sampled (_pick)."""
+    idx = _pick(t.numel(), DUMP_BLOCKS)
+    a = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+    return a.view(np.uint32).astype(np.float64) if unsigned else a.astype(np.float32)
+
+
+def sample_rows(data: torch.Tensor, off: torch.Tensor, length: torch.Tensor, width: int) -> np.ndarray:
+    """(k, width) float32: the bytes of k sampled blocks (_pick; k * width <= DUMP_BYTES), block i read
+    at data[off[i] : off[i] + width] with the bytes at and past length[i] set to 0."""
+    n = off.numel()
+    idx = torch.from_numpy(_pick(n, max(1, min(n, DUMP_BYTES // width)))).to(data.device)
+    col = torch.arange(width, device=data.device)
+    pos = (off[idx].unsqueeze(1) + col).clamp_(max=data.numel() - 1)
+    rows = data[pos] * (col < length[idx].unsqueeze(1))
+    return rows.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(dirname: str, rank: int, arrays: dict) -> None:
+    """DIR/<name>.npy for rank 0's shard (DIR/<name>.rank<r>.npy for the other ranks)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + (".npy" if rank == 0 else f".rank{rank}.npy")), a)
+        log(f"dumped {name}: {a.dtype} {a.shape}")
 
 
 def bench_record_encode(args, rank, world, dev):
@@ -467,8 +540,8 @@ def bench_c5(args):
 
 def bench_compress(args, rank, world, dev, kind, emit: bool = True):
     """Config c3: compress every block of the rank's shard (1 M x 64 KiB image-like by default) with
-    the fused record CRC, inputs resident in HBM.  Verified before timing by a device round trip
-    (compress -> decompress == input) and a CRC recomputation over the outputs."""
+    the fused record CRC, inputs resident in HBM.  With --full verified before timing by a device
+    round trip (compress -> decompress == input) and a CRC recomputation over the outputs."""
     from gobeansdb_amd import batch, shard
     n, bs = args.blocks, args.block_size
     first, _ = shard.weak_shard(rank, n)
@@ -492,32 +565,32 @@ def bench_compress(args, rank, world, dev, kind, emit: bool = True):
     torch.cuda.synchronize()
     log(f"rank {rank}: generated {n} x {bs} B {kind} in {time.time() - t0:.1f}s")
 
-    # ---- correctness gate: round trip on the device, fused CRC == recomputed CRC ----
-    _, cs, st, crc = batch.compress(plain, dst, crc_state=crc_state, max_len=bs, workspace=ws)
-    torch.cuda.synchronize()
-    if int((st != 0).sum().item()):
-        raise SystemExit("compress status")
-    comp = batch.BlockBatch(dst.data, dst.off, cs)
-    if not torch.equal(batch.crc32(comp), crc):
-        raise SystemExit("fused CRC != recomputed CRC")
-    chk = 1 << 14
-    tmp = batch.BlockBatch.empty_for([bs] * chk, device=dev)
-    for c0 in range(0, n, chk):
-        m = min(chk, n - c0)
-        sub = batch.BlockBatch(dst.data, dst.off[c0:c0 + m], cs[c0:c0 + m])
-        out = batch.BlockBatch(tmp.data, tmp.off[:m], tmp.length[:m])
-        _, st2, _ = batch.decompress(sub, out, max_dsize=bs, workspace=ws)
-        o0 = int(poff[c0])
-        if int((st2 != 0).sum().item()) or not torch.equal(tmp.data[:m * bs], plain.data[o0:o0 + m * bs]):
-            raise SystemExit(f"round trip mismatch in blocks {c0}..{c0 + m}")
-    csum = int(cs.to(torch.int64).sum().item())
-    stored = int((dst.data[dst.off] & 1 == 0).sum().item())
-    log(f"device round trip verified; {stored}/{n} blocks stored, out/in {csum / (n * bs):.4f}")
+    if args.full:
+        # ---- correctness gate: round trip on the device, fused CRC == recomputed CRC ----
+        _, cs, st, crc = batch.compress(plain, dst, crc_state=crc_state, max_len=bs, workspace=ws)
+        torch.cuda.synchronize()
+        if int((st != 0).sum().item()):
+            raise SystemExit("compress status")
+        comp = batch.BlockBatch(dst.data, dst.off, cs)
+        if not torch.equal(batch.crc32(comp), crc):
+            raise SystemExit("fused CRC != recomputed CRC")
+        chk = 1 << 14
+        tmp = batch.BlockBatch.empty_for([bs] * chk, device=dev)
+        for c0 in range(0, n, chk):
+            m = min(chk, n - c0)
+            sub = batch.BlockBatch(dst.data, dst.off[c0:c0 + m], cs[c0:c0 + m])
+            out = batch.BlockBatch(tmp.data, tmp.off[:m], tmp.length[:m])
+            _, st2, _ = batch.decompress(sub, out, max_dsize=bs, workspace=ws)
+            o0 = int(poff[c0])
+            if int((st2 != 0).sum().item()) or not torch.equal(tmp.data[:m * bs], plain.data[o0:o0 + m * bs]):
+                raise SystemExit(f"round trip mismatch in blocks {c0}..{c0 + m}")
+        log("device round trip verified")
 
     stream = torch.cuda.current_stream()
+    last = [None]   # what the latest step returned: (dst, csize, status, crc_out)
 
     def step():
-        batch.compress(plain, dst, crc_state=crc_state, max_len=bs, workspace=ws, stream=stream)
+        last[0] = batch.compress(plain, dst, crc_state=crc_state, max_len=bs, workspace=ws, stream=stream)
 
     for _ in range(args.warmup):
         step()
@@ -538,6 +611,18 @@ def bench_compress(args, rank, world, dev, kind, emit: bool = True):
     wall = time.perf_counter() - t_start
     kern_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in evs]))
     wall, kern_ms = shard.max_over_ranks([wall, kern_ms], device=dev)
+    _, cs, st, crc = last[0]
+    if int((st != 0).sum().item()):
+        raise SystemExit("compress status of the last timed step")
+    csum = int(cs.to(torch.int64).sum().item())
+    stored = int((dst.data[dst.off] & 1 == 0).sum().item())
+    log(f"{stored}/{n} blocks stored, out/in {csum / (n * bs):.4f}")
+    if args.dump_outputs:
+        # what a caller of the timed call holds after the last step: the compressed blocks (dst, the
+        # bytes past each block's csize zeroed), their sizes, statuses and fused record CRC32s
+        dump_outputs(args.dump_outputs, rank, {
+            "dst": sample_rows(dst.data, dst.off, cs, bs + 400), "csize": block_array(cs),
+            "status": block_array(st), "crc32": block_array(crc, unsigned=True)})
     tot = shard.sum_over_ranks({"in_bytes": n * bs, "out_bytes": csum}, device=dev)
     value = tot["in_bytes"] * args.steps / wall / 2**30
     achieved = (n * bs + csum) / (kern_ms * 1e-3) / 1e9
@@ -550,7 +635,7 @@ def bench_compress(args, rank, world, dev, kind, emit: bool = True):
             traffic = round(tpb * n)
             traffic_src = f"{os.path.relpath(tj, ROOT)}: {tpb:.0f} B/block (PMC, committed) x {n} blocks"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:  # the CPU leg: rank 0 at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:  # the CPU leg: rank 0 at N = 1 only
         ns = min(256, n)
         dh = dst.data[: int(dst.off[ns - 1]) + bs + 400].cpu().numpy()
         doff = dst.off[:ns].cpu().numpy()

@@ -1,3 +1,4 @@
+import glob
 import json
 import os
 import sys
@@ -18,7 +19,10 @@ def pytest_configure(config):
 class Golden:
     def __init__(self):
         self.manifest = json.load(open(os.path.join(GOLDEN, "golden.json")))
-        self.blob = open(os.path.join(GOLDEN, "qlz_vectors.bin"), "rb").read()
+        # the vector blob is committed in parts (qlz_vectors.0.bin, .1.bin, ...), joined in order
+        nparts = len(glob.glob(os.path.join(GOLDEN, "qlz_vectors.*.bin")))
+        self.blob = b"".join(open(os.path.join(GOLDEN, f"qlz_vectors.{i}.bin"), "rb").read()
+                             for i in range(nparts))
         self.records_data = open(os.path.join(GOLDEN, "records.data"), "rb").read()
 
     def get(self, span):

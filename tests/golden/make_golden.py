@@ -33,6 +33,7 @@ KAT = (b"LZ compression is based on finding repeated strings: Five, six, seven, 
 SIZES = [1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 13, 20, 31, 32, 33, 62, 63, 100, 215, 216, 217, 255,
          256, 300, 1000, 4096, 4097, 16384]
 BIG = [65536]
+PART = 768 << 10   # bytes per committed part of the vector blob
 
 
 def inputs(rng: random.Random):
@@ -87,8 +88,6 @@ def main():
             e["go_len"] = 116   # quicklz_test.go:13 (Go Compress, 9-byte header)
         entries.append(e)
 
-    with open(os.path.join(HERE, "qlz_vectors.bin"), "wb") as f:
-        f.write(blob)
     # ---- records.data (store/datafile.go layout) ----
     recs = []
     data = bytearray()
@@ -125,8 +124,11 @@ def main():
                      "vsz": len(body), "crc": crc, "value": put(value)})
     with open(os.path.join(HERE, "records.data"), "wb") as f:
         f.write(data)
-    with open(os.path.join(HERE, "qlz_vectors.bin"), "wb") as f:
-        f.write(blob)
+    # the vector blob is stored in parts of PART bytes (qlz_vectors.0.bin, .1.bin, ...; conftest.py
+    # joins them in order): the spans in golden.json are offsets into the joined blob
+    for i in range(0, len(blob), PART):
+        with open(os.path.join(HERE, f"qlz_vectors.{i // PART}.bin"), "wb") as f:
+            f.write(blob[i:i + PART])
     manifest = {
         "generator": "tests/golden/make_golden.py",
         "reference": "douban/gobeansdb quicklz/quicklz.c (1.4.1, level 3) + store/crc32.go crc32_write",

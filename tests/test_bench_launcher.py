@@ -52,6 +52,34 @@ def test_main_does_not_shadow_module_functions():
     assert not (local & top), f"main() shadows module functions: {sorted(local & top)}"
 
 
+def test_dump_outputs_sample_is_fixed_masked_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: the sampled block rows are the same from call to call, hold each block's
+    bytes up to its length and zeros past it, stay within the byte budget, and land as
+    float32 / float64 .npy files (host tensors stand in for device memory here)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    data = (torch.arange(4096) % 251).to(torch.uint8)
+    off = torch.tensor([0, 256, 1024, 3840], dtype=torch.int64)
+    length = torch.tensor([10, 256, 300, 5], dtype=torch.int32)
+    rows = bench.sample_rows(data, off, length, 256)
+    assert rows.dtype == np.float32 and rows.shape == (4, 256)
+    for r, o, n in zip(rows, off.tolist(), [10, 256, 256, 5]):   # width 256 cuts the 300-byte block
+        assert np.array_equal(r[:n], data[o:o + n].numpy()) and not r[n:].any()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 512)
+    two = bench.sample_rows(data, off, length, 256)
+    assert two.shape == (2, 256) and np.array_equal(two, bench.sample_rows(data, off, length, 256))
+    pick = bench._pick(1000, 10)
+    assert len(set(pick)) == 10 and list(pick) == sorted(pick) and np.array_equal(pick, bench._pick(1000, 10))
+    crc = bench.block_array(torch.tensor([-1, 7], dtype=torch.int32), unsigned=True)
+    assert crc.dtype == np.float64 and crc.tolist() == [4294967295.0, 7.0]
+    assert bench.block_array(length).dtype == np.float32
+    bench.dump_outputs(str(tmp_path / "d"), 0, {"out": rows, "crc": crc})
+    assert np.array_equal(np.load(tmp_path / "d" / "out.npy"), rows)
+    assert np.load(tmp_path / "d" / "crc.npy").dtype == np.float64
+
+
 def test_c5_one_corpus_split_into_distinct_rounds_at_every_n():
     """bench's c5 leg (tools/bench_c5.py) is strong scaling over ONE corpus: 400 GiB of blocks
     drawn from one seed, split over the ranks by bytes, each share cut into rounds of at most

@@ -11,7 +11,7 @@
 #   single     single-call evidence over 1024 distinct values per size (latency table, 1/16-thread
 #              aggregate of this library and the reference) -> $O/single_call.json, $O/mt.jsonl
 #   rehearsal  the c4/c5 legs at N = 1 and as a 2-rank gloo group on one GPU; digests compared
-#   bench      the default bench line under rocprofv3 --kernel-trace --stats -> $O/bench.json
+#   bench      the bench.py --full line under rocprofv3 --kernel-trace --stats -> $O/bench.json
 #   ab TAG...  parity subset on $TEST_TAG's build, then interleaved c2 timing of the builds
 #              gobeansdb_amd/libqlzx_TAG.so (tools/build_variants.sh; "head" = the in-tree library)
 # Output goes to gpurun_out/${OUT:-r06}; copy what is judged into profiles/ (r06_*).
@@ -101,9 +101,9 @@ step_single() {
 }
 
 step_rehearsal() {
-  timeout -k 10 400 python3 -u bench.py --blocks 65536 --legs-small --no-cpu --steps 3 --warmup 1 \
+  timeout -k 10 400 python3 -u bench.py --full --blocks 65536 --legs-small --no-cpu --steps 3 --warmup 1 \
       > $O/n1.json 2> $O/n1.err || { echo "N=1 failed"; tail -20 $O/n1.err; return 1; }
-  QLZX_BENCH_PG=gloo timeout -k 10 500 python3 -u bench.py --gpus 2 --blocks 65536 --legs-small --no-cpu --steps 3 \
+  QLZX_BENCH_PG=gloo timeout -k 10 500 python3 -u bench.py --gpus 2 --full --blocks 65536 --legs-small --no-cpu --steps 3 \
       --warmup 1 > $O/n2.json 2> $O/n2.err || { echo "N=2 failed"; tail -20 $O/n2.err; return 1; }
   python3 - "$O" <<'PY'
 import json, sys
@@ -116,7 +116,7 @@ PY
 
 step_bench() {
   timeout -k 10 1000 rocprofv3 --kernel-trace --stats -d $O/bench -o bench -- \
-      python3 bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; return 1; }
+      python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; return 1; }
   kstats $O/bench $O/bench_kernel_stats.txt
   find $O/bench -name "*.db" -size +20M -delete
   tail -c 600 $O/bench.json
