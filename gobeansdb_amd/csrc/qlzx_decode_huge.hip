@@ -20,7 +20,13 @@
 // The record CRC (store/datafile.go:161-168) is one wave per 16 KiB segment of the stream plus
 // a GF(2) shift-combine, verified before decoding as readRecordAt does.
 // The host drives the phases (it knows N and M), so a batch holding such values synchronises
-// once per value; values over 64 KiB are rare (the batch path owns the 4-64 KiB ones).
+// once per value; values over 64 KiB are rare (the batch path owns the 4-64 KiB ones).  The
+// drivers are at the end of this file: launch_decode_huge for a batch, huge_one per value.
+#include <algorithm>
+#include <vector>
+
+#include "qlzx_host.h"
+
 namespace qlzx {
 
 constexpr uint32_t kHugeLevels = 8;            // jump tables J_1 .. J_8 (256 groups per jump)
@@ -368,6 +374,154 @@ __global__ void __launch_bounds__(256) k_h_pending(qlzx_blocks b, const int32_t 
         const uint32_t j = atomicAdd(count, 1u);
         items[j] = HugeItem{i, h.csize, h.dsize, h.compressed ? 1u : 0u};
     }
+}
+
+__global__ void k_h_setstatus(int32_t *status, uint32_t *dsize_out, int32_t st, uint32_t ds) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        *status = st;
+        if (dsize_out) *dsize_out = ds;
+    }
+}
+// record CRC verdict of one large block: crc_out, and QLZX_E_CRC (nothing decoded) on a mismatch
+__global__ void k_h_crcverdict(HugeCtl *ctl, const uint32_t *crc_expect, uint32_t *crc_out, int32_t *status,
+                               uint32_t *dsize_out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t c = ~ctl->crc;
+    if (crc_out) *crc_out = c;
+    if (crc_expect && c != *crc_expect) {
+        ctl->st = QLZX_E_CRC;
+        *status = QLZX_E_CRC;
+        if (dsize_out) *dsize_out = 0;
+    }
+}
+__global__ void k_h_crcinit(HugeCtl *ctl, const uint32_t *crc_state) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) ctl->crc = crc_state ? *crc_state : 0xffffffffu;
+}
+
+// One large block (dsize > QLZX_FAST_MAX_DSIZE) by the whole GPU.  The host knows the sizes from
+// the pending list; it synchronises to read the verdict of the parse and the pointer-jumping flags.
+inline int huge_one(const uint8_t *src, uint32_t csize, uint8_t *dst, uint32_t dsize, bool comp, uint32_t max_dsize,
+                    const uint32_t *crc_state, const uint32_t *crc_expect, uint32_t *crc_out, int32_t *status,
+                    uint32_t *dsize_out, uint8_t *ws, hipStream_t s) {
+    HugeWs w;
+    huge_ws_layout(max_dsize, ws, &w);
+    const uint32_t nmax = (uint32_t)huge_nmax(max_dsize);
+    const dim3 G(kHugeGrid), B(kHugeWG);
+    HIP_OK(hipMemsetAsync(w.ctl, 0, sizeof(HugeCtl), s));
+    const bool crc = crc_state || crc_expect || crc_out;
+    if (crc) {
+        hipLaunchKernelGGL(k_h_crcseg, dim3(std::min<uint32_t>((csize + kHugeSeg * 4 - 1) / (kHugeSeg * 4), 1024)),
+                           dim3(256), 0, s, src, (uint64_t)csize, w.scrc);
+        hipLaunchKernelGGL(k_h_crcinit, dim3(1), dim3(64), 0, s, w.ctl, crc_state);
+        // the combine reads the initial state from ctl->crc
+        hipLaunchKernelGGL(k_h_crccomb_ctl, dim3(1), dim3(64), 0, s, w.scrc, (uint64_t)csize, w.ctl);
+        hipLaunchKernelGGL(k_h_crcverdict, dim3(1), dim3(64), 0, s, w.ctl, crc_expect, crc_out, status, dsize_out);
+    }
+    const uint32_t hdr = 9;  // header of a value over 64 KiB: always 9 bytes (quicklz.c:771-772)
+    if (!comp) {  // stored (quicklz.c:808-811)
+        if ((uint64_t)csize < (uint64_t)hdr + dsize) {
+            hipLaunchKernelGGL(k_h_setstatus_ok_if, dim3(1), dim3(64), 0, s, w.ctl, status, dsize_out, QLZX_E_CORRUPT, 0u);
+        } else {
+            hipLaunchKernelGGL(k_h_copy_if, G, B, 0, s, w.ctl, src + hdr, dst, (uint64_t)dsize);
+            hipLaunchKernelGGL(k_h_setstatus_ok_if, dim3(1), dim3(64), 0, s, w.ctl, status, dsize_out, QLZX_OK, dsize);
+        }
+        HIP_OK(hipGetLastError());
+        return QLZX_R_OK;
+    }
+    if (csize > nmax) {  // longer than any stream of dsize bytes can be: trailing garbage (C5)
+        hipLaunchKernelGGL(k_h_setstatus_ok_if, dim3(1), dim3(64), 0, s, w.ctl, status, dsize_out, QLZX_E_CORRUPT, 0u);
+        HIP_OK(hipGetLastError());
+        return QLZX_R_OK;
+    }
+    hipLaunchKernelGGL(k_h_codes, G, B, 0, s, src, csize, w.code);
+    hipLaunchKernelGGL(k_h_delta, G, B, 0, s, src, csize, hdr, (const uint32_t *)w.code, w.delta);
+    hipLaunchKernelGGL(k_h_jump1, G, B, 0, s, (const uint8_t *)w.delta, csize, w.J);
+    for (uint32_t k = 2; k <= kHugeLevels; k++)
+        hipLaunchKernelGGL(k_h_jumpk, G, B, 0, s, (const uint16_t *)(w.J + (size_t)(k - 2) * (nmax + 256)), csize,
+                           w.J + (size_t)(k - 1) * (nmax + 256));
+    hipLaunchKernelGGL(k_h_walk, dim3(1), dim3(64), 0, s, src, csize, hdr, dsize, (const uint32_t *)w.code,
+                       (const uint8_t *)w.delta, (const uint16_t *)w.J, nmax, w.seg, w.ctl);
+    hipLaunchKernelGGL(k_h_expand, G, B, 0, s, (const uint8_t *)w.delta, (const HugeSeg *)w.seg,
+                       (const HugeCtl *)w.ctl, w.glist);
+    hipLaunchKernelGGL(k_h_glen, G, B, 0, s, src, csize, (const uint32_t *)w.code, (const uint32_t *)w.glist,
+                       (const HugeCtl *)w.ctl, w.glen);
+    hipLaunchKernelGGL(k_h_scan, dim3(1), dim3(1024), 0, s, w.glen, (const HugeCtl *)w.ctl);
+    hipLaunchKernelGGL(k_h_items, G, B, 0, s, src, csize, hdr, dsize, (const uint32_t *)w.code,
+                       (const uint32_t *)w.glist, (const uint32_t *)w.glen, w.ctl, w.src, w.lit);
+    HIP_OK(hipGetLastError());
+    HugeCtl h;
+    HIP_OK(hipMemcpyAsync(&h, w.ctl, sizeof(HugeCtl), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (h.st == QLZX_E_CRC) return QLZX_R_OK;  // already reported
+    const bool corrupt = h.st != QLZX_OK || h.bad || !h.done || (h.tail_idx != 0xffffffffu && h.max_match > h.tail_idx);
+    if (corrupt) {
+        hipLaunchKernelGGL(k_h_setstatus, dim3(1), dim3(64), 0, s, status, dsize_out, (int32_t)QLZX_E_CORRUPT, 0u);
+        HIP_OK(hipGetLastError());
+        return QLZX_R_OK;
+    }
+    // pointer jumping, four rounds per check of the last round's flag
+    for (uint32_t r = 0;; r += 4) {
+        if (r + 4 > 64) return fail(QLZX_R_HIP, "huge decode: pointer jumping did not converge");
+        for (uint32_t j = 0; j < 4; j++)
+            hipLaunchKernelGGL(k_h_jumpround, G, B, 0, s, w.src, dsize, w.ctl->changed + r + j);
+        uint32_t ch = 0;
+        HIP_OK(hipMemcpyAsync(&ch, w.ctl->changed + r + 3, 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        if (!ch) break;
+    }
+    hipLaunchKernelGGL(k_h_gather, G, B, 0, s, (const uint32_t *)w.src, (const uint8_t *)w.lit, dsize, dst);
+    hipLaunchKernelGGL(k_h_setstatus, dim3(1), dim3(64), 0, s, status, dsize_out, (int32_t)QLZX_OK, dsize);
+    HIP_OK(hipGetLastError());
+    return QLZX_R_OK;
+}
+
+// The pending list of a batch, as k_h_pending / k_he_pending (qlzx_encode_huge.hip) left it on the
+// device, read back: the count, then the items, then each item's source and destination offset.
+template <typename Item>
+struct PendingList {
+    std::vector<Item> item;
+    std::vector<uint64_t> src_off, dst_off;
+};
+template <typename Item>
+int read_pending(const qlzx_blocks &b, const uint32_t *count, const Item *items, hipStream_t s, PendingList<Item> *p) {
+    uint32_t np = 0;
+    HIP_OK(hipMemcpyAsync(&np, count, 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    p->item.resize(np), p->src_off.resize(np), p->dst_off.resize(np);
+    if (np == 0) return QLZX_R_OK;
+    HIP_OK(hipMemcpyAsync(p->item.data(), items, np * sizeof(Item), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (uint32_t j = 0; j < np; j++) {
+        HIP_OK(hipMemcpyAsync(&p->src_off[j], b.src_off + p->item[j].i, 8, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(&p->dst_off[j], b.dst_off + p->item[j].i, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipStreamSynchronize(s));
+    return QLZX_R_OK;
+}
+
+// The pending large blocks of a batch (K1 left them kPending): listed on the device, read back
+// once, then decoded one at a time by huge_one.  ws: [count 256 | items | huge_ws_layout].
+inline int launch_decode_huge(const qlzx_blocks &b, const uint32_t *crc_state, const uint32_t *crc_expect,
+                              uint32_t *crc_out, int32_t *status, uint32_t *dsize_out, uint32_t max_dsize,
+                              uint8_t *ws, hipStream_t s) {
+    uint32_t *count = (uint32_t *)ws;
+    HugeItem *items = (HugeItem *)(ws + 256);
+    uint8_t *hws = ws + align_up((size_t)b.n * sizeof(HugeItem) + 256, 256);
+    HIP_OK(hipMemsetAsync(count, 0, 4, s));
+    hipLaunchKernelGGL(k_h_pending, dim3(std::min<uint32_t>((b.n + 255) / 256, 4096)), dim3(256), 0, s, b,
+                       (const int32_t *)status, count, items);
+    HIP_OK(hipGetLastError());
+    PendingList<HugeItem> p;
+    if (int r = read_pending(b, count, items, s, &p)) return r;
+    for (size_t j = 0; j < p.item.size(); j++) {
+        const HugeItem &it = p.item[j];
+        const uint32_t i = it.i;
+        if (int r = huge_one(b.src + p.src_off[j], it.csize, b.dst + p.dst_off[j], it.dsize, it.comp != 0, max_dsize,
+                             crc_state ? crc_state + i : nullptr, crc_expect ? crc_expect + i : nullptr,
+                             crc_out ? crc_out + i : nullptr, status + i, dsize_out ? dsize_out + i : nullptr, hws, s))
+            return r;
+    }
+    return QLZX_R_OK;
 }
 
 }  // namespace qlzx

@@ -519,7 +519,10 @@ __device__ __forceinline__ bool small_decode(SmallLds &L, const uint8_t *src, ui
 }
 
 // One block: the small path when it takes the block, else the general latency path
-// (qlzx_decode_solo.hip).
+// (qlzx_decode_solo.hip).  Launched from nowhere: the request service's k_svc_decode takes every
+// block this kernel could (qlzx_single.hip, decompress1).  It stays compiled because the code
+// generated for k_svc_decode differs without it in the unit (same registers and LDS, other
+// block layout; measured 1-2 % slower), so dropping it is a device-code change of its own.
 __global__ void __launch_bounds__(kSoloWG) k_dec_solo(const uint8_t *src, uint32_t len, uint8_t *dst,
                                                      uint32_t dst_cap, uint32_t max_dsize, GroupRec *recs,
                                                      int32_t *status, uint32_t *dsize_out) {
@@ -529,16 +532,6 @@ __global__ void __launch_bounds__(kSoloWG) k_dec_solo(const uint8_t *src, uint32
     } U;
     if (small_decode(U.small, src, len, dst, dst_cap, max_dsize, status, dsize_out)) return;
     solo_decode(U.solo, src, len, dst, dst_cap, max_dsize, recs, status, dsize_out);
-}
-
-// One block (len stream bytes at src, dsize <= QLZX_FAST_MAX_DSIZE, len <= kSoloMaxCsize):
-// recs = kSoloGmax GroupRecs of workspace; status / dsize_out = one device word each.
-inline int launch_decode_solo(const uint8_t *src, uint32_t len, uint8_t *dst, uint32_t dst_cap,
-                              uint32_t max_dsize, GroupRec *recs, int32_t *status, uint32_t *dsize_out,
-                              hipStream_t s) {
-    hipLaunchKernelGGL(k_dec_solo, dim3(1), dim3(kSoloWG), 0, s, src, len, dst, dst_cap, max_dsize, recs,
-                       status, dsize_out);
-    return (int)hipGetLastError();
 }
 
 }  // namespace qlzx

@@ -4,7 +4,7 @@
 // (-mllvm -amdgpu-sched-strategy=iterative-ilp, gobeansdb_amd/build.py): that strategy speeds this
 // kernel up but slows K2 with its CRC prologue, the encoder and the replay kernels, and the
 // strategy is per translation unit (profiles/r05_sched_strategy_ab.txt).  Under QLZX_K2_ONLY the
-// shared sources define no other kernel.  The rest of the library is qlzx_api.hip.
+// shared sources define no other kernel.  The rest of the library is qlzx_api.hip's unit.
 #include <hip/hip_runtime.h>
 
 #include <atomic>

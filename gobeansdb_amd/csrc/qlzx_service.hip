@@ -17,11 +17,13 @@
 //     requests with QLZX_R_HIP instead of leaving the callers spinning.
 // Launches rotate over kSvcStreams streams, so a batch launched while an earlier one still runs
 // does not queue behind it.  Values above kSvcMaxLen (and the Go-compat encoder modes) take the
-// general per-call path in qlzx_api.hip.
+// general per-call path in qlzx_single.hip, which also holds the callers of this service.
 #include <chrono>
 #include <thread>
 #include <vector>
 #include <immintrin.h>
+
+#include "qlzx_host.h"
 
 namespace qlzx {
 
@@ -36,6 +38,7 @@ constexpr uint32_t kSvcMaxLen = 65536;    // dsize / input length served here (s
 constexpr size_t kSvcIn = 80u << 10, kSvcOut = 80u << 10;
 constexpr size_t kSvcHostSlot = kSvcIn + kSvcOut;
 constexpr size_t kSvcRecs = ((size_t)kSoloGmax * sizeof(GroupRec) + 255) & ~(size_t)255;
+static_assert(kSoloGmax * sizeof(GroupRec) <= (1u << 20), "solo records");
 constexpr size_t kSvcDevSlot = kSvcIn + kSvcOut + kSvcRecs;
 static_assert(kSvcIn >= kSoloMaxCsize + 64 && kSvcOut >= kSvcMaxLen + 400 + 64, "slot sizes");
 

@@ -1,4 +1,5 @@
-"""Phase stamps of the single-call latency kernel k_dec_solo (csrc/qlzx_decode_solo.hip) from the
+"""Phase stamps of the single-call latency decoders (solo_decode, csrc/qlzx_decode_solo.hip, and
+small_decode, csrc/qlzx_decode_small.hip, inside the request service's k_svc_decode) from the
 -DQLZX_PROFILE build, plus the host-side split of one qlz_decompress call.
 
 usage: QLZX_LIB=gobeansdb_amd/libqlzx_prof.so python tools/solo_prof.py [calls]
