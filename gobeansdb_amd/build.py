@@ -16,7 +16,7 @@ ARCH = os.environ.get("QLZX_ARCH", "gfx950")
 
 def source_hash() -> str:
     """sha256 (first 16 hex digits) of every csrc/* file, include/qlzx.h and this build script
-    (its compile flags, scheduler strategy and split layout), by name and content, plus the target
+    (its compile flags and scheduler strategy), by name and content, plus the target
     arch: compiled into the library (qlzx_info: "src <hash>"), so a binary is tied to the sources
     and the way they were compiled."""
     h = hashlib.sha256()
@@ -60,23 +60,19 @@ def _run(cmd: list[str], verbose: bool) -> None:
     subprocess.run(cmd, check=True)
 
 
-def _compile(out: str, extra: list[str], verbose: bool, split: bool = True) -> None:
+def _compile(out: str, extra: list[str], verbose: bool) -> None:
+    """The two translation units (qlzx_api.hip; qlzx_k2.hip under K2_SCHED), linked into `out`."""
     # --offload-compress: the gfx950 code object is stored zstd-compressed (1.1 MB instead of
     # 3.8 MB; the HIP runtime inflates it at load)
     base = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "--offload-compress", "-Wall",
             "-Wno-unused-function", "-Wno-unused-parameter", "-I", os.path.join(ROOT, "include")]
-    api = [f"-DQLZX_SRC_HASH=\"{source_hash()}\"", *extra]
-    if not split:  # one translation unit (the profile build: its stamps need qlzx_api.hip's g_prof)
-        _run([*base, "-shared", *api, "-o", out + ".tmp", os.path.join(CSRC, "qlzx_api.hip")], verbose)
-    else:
-        oa, ok2 = out + ".api.o", out + ".k2.o"
-        _run([*base, "-c", *api, "-DQLZX_SPLIT_K2=1", "-DQLZX_SPLIT_K1=1", "-o", oa, os.path.join(CSRC, "qlzx_api.hip")],
-             verbose)
-        _run([*base, "-c", "-DQLZX_SPLIT_K1=1", *extra, *K2_SCHED, "-o", ok2, os.path.join(CSRC, "qlzx_k2.hip")],
-             verbose)
-        _run(["hipcc", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", out + ".tmp", oa, ok2], verbose)
-        for f in (oa, ok2):
-            os.remove(f)
+    oa, ok2 = out + ".api.o", out + ".k2.o"
+    _run([*base, "-c", f"-DQLZX_SRC_HASH=\"{source_hash()}\"", *extra, "-o", oa, os.path.join(CSRC, "qlzx_api.hip")],
+         verbose)
+    _run([*base, "-c", *extra, *K2_SCHED, "-o", ok2, os.path.join(CSRC, "qlzx_k2.hip")], verbose)
+    _run(["hipcc", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", out + ".tmp", oa, ok2], verbose)
+    for f in (oa, ok2):
+        os.remove(f)
     os.replace(out + ".tmp", out)
 
 
@@ -85,7 +81,7 @@ def build(force: bool = False, verbose: bool = False, profile: bool = False) -> 
     if force or _stale():
         _compile(OUT, [], verbose)
     if profile:
-        _compile(PROF_OUT, ["-DQLZX_PROFILE", "-DQLZX_SP_WAVES_PER_EU=1"], verbose, split=False)
+        _compile(PROF_OUT, ["-DQLZX_PROFILE", "-DQLZX_SP_WAVES_PER_EU=1"], verbose)
     return OUT
 
 

@@ -1,7 +1,7 @@
 // qlzx_api.hip -- the C ABI of libqlzx.so (declared in include/qlzx.h): the batch entry points'
 // argument checks and dispatch.  The whole-GPU drivers for values over 64 KiB sit with their
-// kernels (qlzx_decode_huge.hip, qlzx_encode_huge.hip), the single-call entry points in
-// qlzx_single.hip.
+// kernels (qlzx_decode_huge.hip, qlzx_encode_huge.hip), the batch decoder's launcher in
+// qlzx_decode_batch.hip, the single-call entry points in qlzx_single.hip.
 //
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.
@@ -16,7 +16,10 @@
 
 #include "qlzx_tables.hip"
 #include "qlzx_crc.hip"
-#include "qlzx_decode_wave.hip"
+#include "qlzx_synth.hip"
+#include "qlzx_decode_solo.hip"
+#include "qlzx_decode_small.hip"
+#include "qlzx_decode_batch.hip"
 #include "qlzx_decode_lane8.hip"
 #include "qlzx_decode_huge.hip"
 #include "qlzx_encode_lane.hip"
@@ -33,10 +36,11 @@ static constexpr uint32_t kMaxLaneSlabs = 4096;  // concurrent lane encoders for
 
 #ifdef QLZX_PROFILE
 namespace qlzx {
-__device__ unsigned long long *g_prof = nullptr;
+int k2_profile_set(void *dev_buf);  // qlzx_k2.hip
 }
-extern "C" int qlzx_profile_set(void *dev_buf) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(qlzx::g_prof), &dev_buf, sizeof(void *));
+extern "C" int qlzx_profile_set(void *dev_buf) {  // g_prof of both translation units
+    if (const int e = (int)hipMemcpyToSymbol(HIP_SYMBOL(qlzx::g_prof), &dev_buf, sizeof(void *))) return e;
+    return qlzx::k2_profile_set(dev_buf);
 }
 #endif
 
@@ -87,10 +91,10 @@ int qlz_get_setting(int setting) {  // quicklz.c:31-58 as built by quicklz.h:25-
 /* ---------------- batch device API ---------------- */
 
 size_t qlzx_decompress_workspace_size(uint32_t n, uint32_t max_dsize) {
-    // two halves for batches of more than one chunk: K1/K2 of consecutive chunks overlap (three
+    // two regions for batches of more than one chunk: K1/K2 of consecutive chunks overlap (three
     // for mixed sizes over three chunks or more: the last chunk's K1 starts first)
-    const size_t one = qlzx::decode_wave_ws_bytes(n, max_dsize);
-    size_t ws = qlzx::decode_wave_halves(n, max_dsize) * one;
+    const qlzx::BatchLayout L = qlzx::batch_layout(n, max_dsize);
+    size_t ws = L.regions * L.one;
     if (max_dsize > QLZX_FAST_MAX_DSIZE)  // large values: the pending list and the whole-GPU decoder
         ws += align_up((size_t)n * sizeof(qlzx::HugeItem) + 256, 256) + qlzx::huge_ws_layout(max_dsize, nullptr, nullptr);
     return ws;
@@ -106,7 +110,7 @@ int qlzx_decompress_batch(const qlzx_blocks *b, const uint32_t *dst_cap, uint32_
         return fail(QLZX_R_BAD_ARG, "qlzx_decompress_batch: null block array");
     hipStream_t s = (hipStream_t)stream;
     // no workspace: the general lane-per-block kernel for every block
-    const bool fast = workspace && workspace_bytes >= qlzx::decode_wave_ws_bytes(b->n, max_dsize);
+    const bool fast = workspace && workspace_bytes >= qlzx::batch_layout(b->n, max_dsize).one;
     if (fast) {
         int r = qlzx::launch_decode_wave(*b, dst_cap, dsize, status, crc_state, crc_expect, crc_out,
                                          max_dsize, workspace, workspace_bytes, s);

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "qlzx_decode_batch.h"
 #include "qlzx_host.h"
 
 namespace qlzx {

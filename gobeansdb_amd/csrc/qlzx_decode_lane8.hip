@@ -2,7 +2,7 @@
 // output written straight to the block's destination with 8-byte wild copies.
 //
 // This is the catch-all path: any dsize, including BodyMax = 50 MiB values
-// (config/mc_config.go:7); the batch fast path (qlzx_decode_wave.hip) owns
+// (config/mc_config.go:7); the batch fast path (qlzx_decode_batch.hip) owns
 // blocks up to QLZX_FAST_MAX_DSIZE.  Each lane walks its block's control-word /
 // token chain (quicklz.c:513-671) and executes it directly: the history is the
 // destination buffer itself, so a match source is an earlier part of the

@@ -17,8 +17,12 @@
 //   4. GroupRecs {ip, m, a, b}, then items, markers, fill, pointer jumping and gather exactly as
 //      qlzx_decode_solo.hip steps 4-8 (the checks C3-C5 included), with the literal bytes and
 //      sources in LDS and the result written once to the destination (the caller's slot).
-// Statuses and bytes equal the batch decoder's (K1 + K2, qlzx_decode_v4.hip) on the same stream,
+// Statuses and bytes equal the batch decoder's (K1 + K2, qlzx_decode_k1.h and qlzx_decode_k2.h) on the same stream,
 // dsize-0 rule included (tests/test_gpu_solo.py).
+#pragma once
+#include "qlzx_decode_batch.h"
+#include "qlzx_decode_solo.hip"  // kSoloWG, tok_code
+
 namespace qlzx {
 
 constexpr uint32_t kSmC = 17408;                 // stream bytes (csize bound of this path)

@@ -15,7 +15,7 @@
 //                 group may run past the stream;  j2[x] = delta[x] + delta[x + delta[x]];
 //   3. one lane follows hdr -> hdr + j2[hdr] -> ... (two groups per LDS read) and lists the
 //      group starts; a group without a shortcut is parsed byte by byte there as K1 parses it
-//      (qlzx_decode_wave.hip k_dec_parse: checks C1, C2, the group bound, the item count);
+//      (qlzx_decode_k1.h k_dec_parse6: checks C1, C2, the group bound, the item count);
 //   4. the GroupRec {ip, m, a, b} of every listed group, in parallel.
 //   DECODE (quicklz.c:531-671 restated output-parallel, as K2b does per chunk)
 //   5. items: each thread decodes a contiguous run of items (token from its GroupRec), a
@@ -29,6 +29,9 @@
 //      literal (log2 of the longest copy chain rounds);
 //   8. gather: out[p] = out[s[p]] (the literal bytes written in 5).
 // Status and output equal K1 + K2b's on the same stream (tests/test_gpu_solo.py).
+#pragma once
+#include "qlzx_decode_batch.h"
+
 namespace qlzx {
 
 constexpr uint32_t kSoloWG = 1024;

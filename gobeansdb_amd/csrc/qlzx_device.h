@@ -31,6 +31,10 @@ extern __device__ uint32_t g_crc_piece[64];
 // g_crc_byte[j] = x^(8 j); g_crc_stripe[k] = x^(8 * 4096 * k).
 extern __device__ uint32_t g_crc_byte[64];
 extern __device__ uint32_t g_crc_stripe[64];
+// Multiply-by-constant tables of wave_crc / wave_crc_rep (built in qlzx_tables.hip).
+constexpr int kMulTabs = 7;
+extern __device__ uint32_t g_crc_mul[kMulTabs * 1024];
+extern __device__ uint32_t g_crc_mul32[1024];
 
 constexpr uint32_t CRC_POLY = 0xEDB88320u;
 
@@ -116,7 +120,8 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) { return (uint32_t)(
 // Stamps are s_memtime (shader clock) deltas summed per phase into a debug
 // buffer; they never feed any output.  Release builds compile them away.
 #ifdef QLZX_PROFILE
-extern __device__ unsigned long long *g_prof;
+// one pointer per translation unit (no relocatable device code); qlzx_profile_set sets them all
+static __device__ unsigned long long *g_prof = nullptr;
 #define PROF_DECL unsigned long long _pt = __builtin_amdgcn_s_memtime(), _pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define PROF_MARK(ph)                                             \
     do {                                                          \

@@ -1,12 +1,32 @@
 // qlzx_host.h -- what the host code of qlzx_api.hip's unit shares: the calling thread's error text
-// (qlzx_last_error), the HIP_OK early return and two small helpers.  Included by the files that
-// hold host drivers (qlzx_decode_huge.hip, qlzx_encode_huge.hip, qlzx_service.hip,
-// qlzx_single.hip, qlzx_api.hip); qlzx_k2.hip's unit has no use for it.
+// (qlzx_last_error), the HIP_OK early return, two small helpers and what the per-thread HIP objects
+// (the batch launcher's side streams, the single-call contexts) need at process exit.  Included by
+// the files that hold host drivers (qlzx_decode_batch.hip, qlzx_decode_huge.hip,
+// qlzx_encode_huge.hip, qlzx_service.hip, qlzx_single.hip, qlzx_api.hip); qlzx_k2.hip's unit has
+// no use for it.
 #pragma once
 
+#include <atomic>
+#include <cstdlib>
+#include <mutex>
 #include <string>
 
 #include "qlzx_device.h"
+
+namespace qlzx {
+
+constexpr uint32_t kMaxDevices = 64;  // devices with per-thread or per-process state of their own
+
+// Set by an atexit handler registered once the runtime is in use (after HIP registered its own
+// teardown; atexit runs in reverse order): per-thread HIP objects destroyed after that (threads
+// exiting during process exit) are left to the runtime's teardown.
+inline std::atomic<bool> g_hip_down{false};
+inline void note_hip_up() {
+    static std::once_flag once;
+    std::call_once(once, [] { std::atexit([] { g_hip_down.store(true); }); });
+}
+
+}  // namespace qlzx
 
 namespace {
 

@@ -33,7 +33,7 @@ struct RpCounters {
 };
 
 // 1-2. slot classification (readRecordAt's size checks, store/datafile.go:128-136) and the
-// record CRC of every candidate, one wave each (wave_crc of qlzx_crc.hip).  A wave
+// record CRC of every candidate, one wave each (wave_crc of qlzx_crc.h).  A wave
 // takes ~3 us per 4 KiB stripe, so a candidate longer than kRpLong (a false candidate can
 // claim up to BodyMax = 50 MiB) would be one wave's serial tail for the whole launch: those go
 // to a list (lng[], their per-list XOR accumulator and segment counter zeroed here) and are

@@ -105,7 +105,6 @@ __device__ uint32_t g_crc_stripe[64] = {T64(stripe)};
 // x^(8 kMulBytes[i]) mod P, so a register c times that power is four lookups, one per byte.
 // i = 0..5: 64 * 2^i bytes (the lane-combine tree), i = 6: 4032 bytes (the other 63 lanes'
 // pieces of a 4 KiB stripe).
-constexpr int kMulTabs = 7;
 struct CrcMul {
     uint32_t t[kMulTabs * 1024];
 };

@@ -22,7 +22,7 @@ def test_library_builds_and_exports_header_symbols():
 
 def test_gfx950_code_object_present(tmp_path):
     # the fat binary section (.hip_fatbin) holds one zstd-compressed offload bundle ("CCOB") per
-    # translation unit (qlzx_api.hip and qlzx_k2.hip since round 5): each carries a gfx950 code
+    # translation unit (qlzx_api.hip; qlzx_k2.hip with K1 and K2 of the batch decoder): each carries a gfx950 code
     # object -- list every bundle's entries with the ROCm LLVM tools
     import re
     bin_dir = "/opt/rocm/lib/llvm/bin"
@@ -104,3 +104,51 @@ def test_service_test_hook_is_inert_by_default():
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
     assert p.returncode == 0, p.stderr
     assert "rc -1" in p.stdout and "test hooks are off" in p.stdout, p.stdout
+
+
+# (n, max_dsize, chunks, regions, bytes) of qlzx_decompress_workspace_size for max_dsize <= 64 KiB
+# (larger values add the whole-GPU decoder's own layout)
+WS_PINS = [
+    (0, 16384, 1, 1, 10240),
+    (1, 3, 1, 1, 2048),
+    (1, 16384, 1, 1, 10496),
+    (64, 16384, 1, 1, 545280),
+    (65, 4096, 1, 1, 142592),
+    (5, 65536, 1, 1, 171264),
+    (262144, 16384, 1, 1, 2228225280),
+    (262145, 16384, 2, 2, 4456451072),
+    (524289, 16384, 3, 2, 4458548224),
+    (1048576, 16384, 4, 2, 4462742016),
+    (131072, 16385, 1, 1, 1114113280),
+    (131073, 16385, 2, 2, 2228227072),
+    (262144, 65536, 2, 2, 8881441280),
+    (262145, 32768, 3, 3, 6672093696),
+    (393217, 65536, 4, 3, 13323735552),
+    (1000000, 65536, 8, 3, 13331016192),
+]
+
+
+def _ws_restated(n, md):
+    """The batch decoder's workspace restated term by term: (chunks, regions, terms of a region)."""
+    a = lambda x: (x + 255) & ~255
+    cb = 262144 if md <= 16384 else 131072
+    c = min(max(n, 1), cb)
+    terms = {"info": a(16 * c), "recs": a(16 * c * (min(md, 65536) // 31 + 2)), "order": a(4 * n), "aux": 1280}
+    chunks = 1 if n <= cb else 1 + -(-(n - cb) // cb)
+    regions = 1 if chunks == 1 else 2 + (1 if md > 16384 and chunks >= 3 else 0)
+    return chunks, regions, terms
+
+
+def test_decompress_workspace_size_pinned():
+    """qlzx_decompress_workspace_size is part of the ABI: callers size their buffers by it, and the
+    launcher cuts its regions from the same layout.  Pinned values, and the restatement beside
+    them so that a failure shows which term moved."""
+    L = _lib.lib()
+    L.qlzx_decompress_workspace_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    L.qlzx_decompress_workspace_size.restype = ctypes.c_size_t
+    for n, md, chunks, regions, want in WS_PINS:
+        got_chunks, got_regions, terms = _ws_restated(n, md)
+        assert (got_chunks, got_regions) == (chunks, regions), (n, md)
+        assert regions * sum(terms.values()) == want, (n, md, terms)
+        got = L.qlzx_decompress_workspace_size(n, md)
+        assert got == want, (n, md, got, want, regions, terms)

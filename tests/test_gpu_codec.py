@@ -260,7 +260,7 @@ def test_batch_crc_verify_every_length(cuda, max_dsize):
 # first in a third workspace region)
 @pytest.mark.parametrize("crc,mixed", [(False, False), (True, False), (False, True), (True, True), (False, 4)])
 def test_multi_chunk_overlap_round_trip(cuda, crc, mixed):
-    """More blocks than one decode chunk (chunk_blocks in qlzx_decode_wave.hip): K1 of chunk c+1
+    """More blocks than one decode chunk (chunk_blocks in qlzx_decode_batch.h): K1 of chunk c+1
     runs on the side stream while K2 of chunk c runs.  Every block must round-trip, and with crc
     the fused record CRC must equal a separate CRC pass over the compressed values."""
     import torch
@@ -270,7 +270,7 @@ def test_multi_chunk_overlap_round_trip(cuda, crc, mixed):
     max_dsize = 32768 if mixed else max(lens)
     if mixed:  # three (four) chunks: a region more for the last (two) chunks' early K1s
         L = _lib.lib()
-        regions = 3  # one early chunk (QLZX_LAST_K1_EARLY) at three chunks and at four
+        regions = 3  # one early chunk at three chunks and at four
         assert L.qlzx_decompress_workspace_size(n, max_dsize) > \
             (regions + 0.2) * L.qlzx_decompress_workspace_size(100000, max_dsize)
     plain = batch.synth("text", 77, lens)
@@ -293,6 +293,63 @@ def test_multi_chunk_overlap_round_trip(cuda, crc, mixed):
     assert torch.equal(out.data[pos], plain.data[pos])
     if crc:
         assert torch.equal(crc_out, batch.crc32(src))
+
+
+_TINY = {}
+
+
+def _tiny_blocks():
+    """262144 + 65 = 2 * 131072 + 65 compressed text blocks of 40-300 bytes (built once): one
+    uniform chunk and two K1 waves, one of them partial; or two mixed chunks and the same."""
+    if not _TINY:
+        import torch
+        from gobeansdb_amd import batch
+        n = 262144 + 65
+        lens = [40 + (i * 37) % 261 for i in range(n)]
+        plain = batch.synth("text", 78, lens)
+        comp, cs, st, _ = batch.compress(plain, max_len=max(lens))
+        assert int((st != 0).sum()) == 0
+        src = batch.BlockBatch(comp.data, comp.off, cs)
+        torch.cuda.synchronize()
+        _TINY.update(lens=lens, plain=plain, src=src, plain_crc=batch.crc32(plain), src_crc=batch.crc32(src))
+    return _TINY
+
+
+# (max_dsize, regions the ABI asks for, regions the caller gives)
+@pytest.mark.parametrize("crc", [False, True])
+@pytest.mark.parametrize("max_dsize,regions,given", [(2048, 2, 1), (16385, 3, 2)])
+def test_multi_chunk_under_provisioned_workspace(cuda, max_dsize, regions, given, crc):
+    """A caller may give fewer workspace regions than qlzx_decompress_workspace_size asks for.
+    Uniform sizes, two chunks, one region of two: every chunk's K1 and K2 run on the caller's
+    stream, one after another.  Mixed sizes, three chunks, two regions of three: K1 and K2 of
+    consecutive chunks overlap, but the last chunk's K1 does not start early.  Either way every
+    block decodes."""
+    import torch
+    from gobeansdb_amd import _lib, batch
+    t = _tiny_blocks()
+    src, n = t["src"], t["src"].n
+    L = _lib.lib()
+    full = L.qlzx_decompress_workspace_size(n, max_dsize)
+    assert full % regions == 0
+    ws_bytes = full // regions * given
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    out = batch.BlockBatch.empty_for(t["lens"])
+    dsize = torch.zeros(n, dtype=torch.int32, device="cuda")
+    status = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    state = torch.full((n,), -1, dtype=torch.int32, device="cuda") if crc else None
+    crc_out = torch.zeros(n, dtype=torch.int32, device="cuda") if crc else None
+    b = _lib.Blocks(src.data.data_ptr(), src.off.data_ptr(), src.length.data_ptr(), out.data.data_ptr(),
+                    out.off.data_ptr(), n)
+    rc = L.qlzx_decompress_batch(ctypes.byref(b), None, dsize.data_ptr(), status.data_ptr(),
+                                 state.data_ptr() if crc else None, None, crc_out.data_ptr() if crc else None,
+                                 max_dsize, ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
+    _lib.check(rc, "qlzx_decompress_batch")
+    torch.cuda.synchronize()
+    assert int((status != 0).sum()) == 0
+    assert torch.equal(dsize, t["plain"].length)
+    assert torch.equal(batch.crc32(out), t["plain_crc"])
+    if crc:
+        assert torch.equal(crc_out, t["src_crc"])
 
 
 def test_mixed_sizes_block_order_round_trip(cuda):

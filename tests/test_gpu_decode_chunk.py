@@ -1,4 +1,4 @@
-"""GPU parity for the byte-parallel K2 (k_dec_chunk4, qlzx_decode_v4.hip) on inputs built to
+"""GPU parity for the byte-parallel K2 (k_dec_chunk4, qlzx_decode_k2.h) on inputs built to
 stress its three mechanisms, against the oracle-compressed stream of the same input:
 
 * in-chunk sources resolved by pointer jumping: periodic data (short periods give chains of

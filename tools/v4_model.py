@@ -1,4 +1,4 @@
-"""CPU model of the round-4 decoder pair (qlzx_decode_v4.hip), lane for lane (tools only).
+"""CPU model of the round-4 decoder pair (qlzx_decode_k1.h, qlzx_decode_k2.h), lane for lane (tools only).
 
 K1 (k_dec_parse4): one lane's step loop over a whole stream (no ring: every byte is "landed").
 K2 (k_dec_chunk4): the wave's batches (64 items) and chunks (256 B) with the u32 key ring, the
