@@ -21,6 +21,11 @@ OK, E_SIZE_COMPRESSED, E_CORRUPT, E_LEVEL, E_DST_CAP, E_CRC, E_HEADER, E_EMPTY, 
 STATUS_NAMES = ["OK", "E_SIZE_COMPRESSED", "E_CORRUPT", "E_LEVEL", "E_DST_CAP", "E_CRC",
                 "E_HEADER", "E_EMPTY", "E_TOO_LARGE", "E_MAX_DSIZE", "E_RUNTIME"]
 
+# enum qlzx_read_status (qlzx_read_plan's verdict per request)
+RD_OK, RD_ALIGN, RD_EOF_HEADER, RD_KEY_SIZE, RD_VALUE_SIZE, RD_EOF_BODY, RD_CRC = range(7)
+RD_NAMES = ["RD_OK", "RD_ALIGN", "RD_EOF_HEADER", "RD_KEY_SIZE", "RD_VALUE_SIZE", "RD_EOF_BODY", "RD_CRC"]
+# enum qlzx_return
+R_OK, R_BAD_ARG, R_WORKSPACE, R_HIP, R_NO_DEVICE = 0, -1, -2, -3, -4
 
 F_GO_COMPAT = 1
 F_LEVEL1 = 2
@@ -107,6 +112,12 @@ def lib() -> ctypes.CDLL:
     L.qlzx_replay_plan.restype = ctypes.c_int
     L.qlzx_replay_finish.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
     L.qlzx_replay_finish.restype = ctypes.c_int
+    L.qlzx_read_plan_workspace_size.argtypes = [u32]
+    L.qlzx_read_plan_workspace_size.restype = sz
+    L.qlzx_read_plan.argtypes = [vp, u64, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.qlzx_read_plan.restype = ctypes.c_int
+    L.qlzx_read_finish.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.qlzx_read_finish.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

@@ -26,6 +26,7 @@
 #include "qlzx_encode_wg.hip"
 #include "qlzx_encode_huge.hip"
 #include "qlzx_replay.hip"
+#include "qlzx_read.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -305,6 +306,52 @@ int qlzx_replay_finish(const uint8_t *data, const uint64_t *rec_off, const uint3
                                              comp_dst_off, outbuf, cap, flag, value_len, in_out, val_off, vhash,
                                              (hipStream_t)stream);
     if (e) return fail(QLZX_R_HIP, "qlzx_replay_finish", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+size_t qlzx_read_plan_workspace_size(uint32_t n) { return qlzx::read_ws_layout(n, nullptr, nullptr); }
+
+int qlzx_read_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, uint32_t n, uint32_t max_key,
+                   uint64_t body_max, const uint8_t *want_key, const uint64_t *want_key_off,
+                   const uint32_t *want_key_len, int32_t *rd_status, uint8_t *key_eq, int32_t *hdr,
+                   uint32_t *comp_idx, uint64_t *comp_off, uint32_t *comp_len, uint32_t *comp_dsize,
+                   uint64_t *comp_dst_off, uint32_t *totals, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!totals) return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: null totals");
+    if (n) {
+        if ((!data && size) || !rec_off || !rd_status || !hdr || !comp_idx || !comp_off || !comp_len || !comp_dsize ||
+            !comp_dst_off)
+            return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: null arg");
+        const int nkeys = !!want_key + !!want_key_off + !!want_key_len;
+        if (nkeys != 0 && nkeys != 3) return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: want_key* are all three or none");
+        if ((nkeys == 3) != (key_eq != nullptr))
+            return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: key_eq goes with the wanted keys");
+        if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: file too large");
+        if (body_max > 0xffffffffull - 24 - max_key)
+            return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: 24 + max_key + body_max is 4 GiB or more");
+        if (!workspace || workspace_bytes < qlzx_read_plan_workspace_size(n))
+            return fail(QLZX_R_WORKSPACE, "qlzx_read_plan: workspace too small");
+    }
+    const int e = qlzx::launch_read_plan(data, size, rec_off, n, max_key, body_max, want_key, want_key_off,
+                                         want_key_len, rd_status, key_eq, hdr, comp_idx, comp_off, comp_len,
+                                         comp_dsize, comp_dst_off, totals, workspace, (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_read_plan", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+int qlzx_read_finish(const uint8_t *data, const uint64_t *rec_off, uint32_t n, const int32_t *rd_status,
+                     const uint32_t *totals, const uint32_t *comp_idx, const int32_t *comp_status,
+                     const uint32_t *comp_dsize, const uint64_t *comp_dst_off, const uint8_t *outbuf,
+                     int32_t *flag, int32_t *value_len, uint8_t *in_out, uint64_t *val_off, uint16_t *vhash,
+                     int32_t *dec_status, void *stream) {
+    if (n == 0) return QLZX_R_OK;
+    // data and outbuf may be null: nothing of them is read when no request passed / none decoded
+    if (!rec_off || !rd_status || !totals || !comp_idx || !comp_status || !comp_dsize || !comp_dst_off || !flag ||
+        !value_len || !in_out || !val_off || !vhash || !dec_status)
+        return fail(QLZX_R_BAD_ARG, "qlzx_read_finish: null arg");
+    const int e = qlzx::launch_read_finish(data, rec_off, n, rd_status, totals, comp_idx, comp_status, comp_dsize,
+                                           comp_dst_off, outbuf, flag, value_len, in_out, val_off, vhash, dec_status,
+                                           (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_read_finish", (hipError_t)e);
     return QLZX_R_OK;
 }
 

@@ -107,11 +107,21 @@ __global__ void __launch_bounds__(256) k_rp_scan(const uint8_t *data, uint64_t s
 // global segment sequence with g = wave id (mod all waves).  A segment's raw CRC, shifted over
 // the bytes after it, is XORed into its candidate's accumulator, and the wave that completes
 // the last segment (counter == nseg) turns the sum into the verdict.
-__global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const RpCounters *cnt,
-                                                     uint32_t *rsz, const uint32_t *lng, uint32_t *lacc,
-                                                     uint32_t *ldone) {
+// What a list entry names and where its verdict goes is the policy P's: rec(data, e) is the
+// entry's record, verdict(h, e, ksz, vsz, reg) takes the finished CRC register.  Replay lists
+// chunk slots (RpLongSlots); the batched read lists request indices (RdLongReqs, qlzx_read.hip).
+struct RpLongSlots {
+    uint32_t *rsz;
+    __device__ const uint8_t *rec(const uint8_t *data, uint32_t s) const { return data + (uint64_t)s * kRpSlot; }
+    __device__ void verdict(const uint8_t *h, uint32_t s, uint32_t ksz, uint32_t vsz, uint32_t reg) const {
+        rp_crc_verdict(h, s, ksz, vsz, reg, rsz);
+    }
+};
+template <class P>
+__global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const uint32_t *nlong, P pol,
+                                                     const uint32_t *lng, uint32_t *lacc, uint32_t *ldone) {
     __shared__ uint32_t tab[kCrcLdsWords];
-    const uint32_t nl = cnt->nlong;
+    const uint32_t nl = *nlong;
     if (nl == 0) return;
     load_crc_lds(tab);
     __syncthreads();
@@ -123,7 +133,7 @@ __global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const 
         uint32_t s = 0, len = 0;
         if (e < nl) {
             s = lng[e];
-            const uint2 kv = *(const uint2 *)(data + (uint64_t)s * kRpSlot + 16);
+            const uint2 kv = *(const uint2 *)(pol.rec(data, s) + 16);
             len = 20 + kv.x + kv.y;
         }
         const uint32_t ns = (len + kRpSeg - 1) / kRpSeg;
@@ -139,7 +149,7 @@ __global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const 
             const uint32_t nseg = __shfl(ns, L, 64);
             const uint32_t o = (r - (__shfl(inc, L, 64) - nseg)) * kRpSeg;
             const uint32_t sl = sl_len - o < kRpSeg ? sl_len - o : kRpSeg;
-            const uint8_t *h = data + (uint64_t)sl_s * kRpSlot;
+            const uint8_t *h = pol.rec(data, sl_s);
             // segment 0 carries the initial state; each register is shifted over the rest
             const uint32_t raw = crc_shift(wave_crc(tab, h + 4 + o, sl, o ? 0u : 0xffffffffu, lane), sl_len - o - sl);
             if (lane == 0) {
@@ -148,7 +158,7 @@ __global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const 
                 if (atomicAdd(&ldone[e0 + L], 1u) == nseg - 1) {
                     __threadfence();
                     const uint2 kv = *(const uint2 *)(h + 16);
-                    rp_crc_verdict(h, sl_s, kv.x, kv.y, atomicOr(&lacc[e0 + L], 0u), rsz);
+                    pol.verdict(h, sl_s, kv.x, kv.y, atomicOr(&lacc[e0 + L], 0u));
                 }
             }
         }
@@ -445,11 +455,23 @@ __global__ void __launch_bounds__(1024) k_rp_dstoff(const uint32_t *comp_dsize, 
 }
 // After the batch decode of the compressed records: flag, value length, where the value lives
 // (decompressed buffer or the raw body: Payload.Decompress errors are swallowed, store/item.go:
-// 163-176) and Getvhash of every record.
-__global__ void __launch_bounds__(256) k_rp_finish_vals(const uint8_t *data, const uint64_t *off, const uint32_t *result,
+// 163-176) and Getvhash of every record.  Which entries of off[] are records is the predicate
+// V's (n() entries, ok(j)): replay's list holds records only (RpAllRecords); the batched read's
+// holds requests that may have failed (RdOkRequests, qlzx_read.hip), which get zeros.
+struct RpAllRecords {
+    const uint32_t *result;
+    __device__ uint32_t n() const { return result[0]; }
+    __device__ bool ok(uint32_t) const { return true; }
+};
+template <class V>
+__global__ void __launch_bounds__(256) k_rp_finish_vals(const uint8_t *data, const uint64_t *off, V valid,
                                                        int32_t *flag, int32_t *value_len, uint8_t *in_out,
                                                        uint64_t *val_off) {
-    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < result[0]; j += gridDim.x * 256) {
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < valid.n(); j += gridDim.x * 256) {
+        if (!valid.ok(j)) {
+            flag[j] = 0, value_len[j] = 0, in_out[j] = 0, val_off[j] = 0;
+            continue;
+        }
         const uint32_t *h = (const uint32_t *)(data + off[j]);  // every record: the stored body first
         flag[j] = (int32_t)h[2];
         value_len[j] = (int32_t)h[5];
@@ -460,20 +482,26 @@ __global__ void __launch_bounds__(256) k_rp_finish_vals(const uint8_t *data, con
 __global__ void __launch_bounds__(256) k_rp_finish_comp(const uint32_t *ncomp_p, const uint32_t *comp_idx,
                                                        const int32_t *cstatus, const uint32_t *cdsize,
                                                        const uint64_t *cdst_off, int32_t *flag, int32_t *value_len,
-                                                       uint8_t *in_out, uint64_t *val_off) {
+                                                       uint8_t *in_out, uint64_t *val_off, int32_t *dec_status) {
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < *ncomp_p; k += gridDim.x * 256) {
-        if (cstatus[k] != QLZX_OK) continue;
         const uint32_t j = comp_idx[k];
+        if (dec_status) dec_status[j] = cstatus[k];  // the error the reference only logs
+        if (cstatus[k] != QLZX_OK) continue;
         flag[j] -= (int32_t)kFlagCompress;  // store/item.go:172-174
         value_len[j] = (int32_t)cdsize[k];
         in_out[j] = 1;
         val_off[j] = cdst_off[k];
     }
 }
-__global__ void __launch_bounds__(256) k_rp_vhash2(const uint8_t *data, const uint8_t *outbuf, const uint32_t *result,
+template <class V>
+__global__ void __launch_bounds__(256) k_rp_vhash2(const uint8_t *data, const uint8_t *outbuf, V valid,
                                                   const uint8_t *in_out, const uint64_t *val_off,
                                                   const int32_t *value_len, uint16_t *vh) {
-    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < result[0]; j += gridDim.x * 256) {
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < valid.n(); j += gridDim.x * 256) {
+        if (!valid.ok(j)) {
+            vh[j] = 0;
+            continue;
+        }
         const uint8_t *v = (in_out[j] ? outbuf : data) + val_off[j];
         const uint32_t l = (uint32_t)value_len[j];
         uint32_t h = l * 97u;
@@ -516,12 +544,12 @@ inline int launch_replay_finish(const uint8_t *data, const uint64_t *off, const 
                                 uint16_t *vh, hipStream_t s) {
     if (cap == 0) return 0;
     const uint32_t grid = std::min<uint32_t>((cap + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_rp_finish_vals, dim3(grid), dim3(256), 0, s, data, off, result, flag, value_len, in_out,
-                       val_off);
-    hipLaunchKernelGGL(k_rp_finish_comp, dim3(grid), dim3(256), 0, s, totals + 1, comp_idx, cstatus, cdsize, cdst_off,
+    hipLaunchKernelGGL(k_rp_finish_vals<RpAllRecords>, dim3(grid), dim3(256), 0, s, data, off, RpAllRecords{result},
                        flag, value_len, in_out, val_off);
-    hipLaunchKernelGGL(k_rp_vhash2, dim3(grid), dim3(256), 0, s, data, outbuf, result, (const uint8_t *)in_out,
-                       (const uint64_t *)val_off, (const int32_t *)value_len, vh);
+    hipLaunchKernelGGL(k_rp_finish_comp, dim3(grid), dim3(256), 0, s, totals + 1, comp_idx, cstatus, cdsize, cdst_off,
+                       flag, value_len, in_out, val_off, (int32_t *)nullptr);
+    hipLaunchKernelGGL(k_rp_vhash2<RpAllRecords>, dim3(grid), dim3(256), 0, s, data, outbuf, RpAllRecords{result},
+                       (const uint8_t *)in_out, (const uint64_t *)val_off, (const int32_t *)value_len, vh);
     return (int)hipGetLastError();
 }
 
@@ -578,7 +606,8 @@ inline int launch_replay_index(const uint8_t *data, uint64_t size, uint64_t star
     if (nslots)
         hipLaunchKernelGGL(k_rp_scan, dim3(scan_grid), dim3(256), 0, s, data, size, nslots, max_key, body_max, w.kind,
                            w.rsz, w.cnt, w.vis, w.J, w.J2);
-    hipLaunchKernelGGL(k_rp_crc_long, dim3(2048), dim3(256), 0, s, data, w.cnt, w.rsz, w.vis, w.J, w.J2);
+    hipLaunchKernelGGL(k_rp_crc_long<RpLongSlots>, dim3(2048), dim3(256), 0, s, data,
+                       (const uint32_t *)&w.cnt->nlong, RpLongSlots{w.rsz}, (const uint32_t *)w.vis, w.J, w.J2);
     // valid slots in order: vidx (exclusive count) and A
     ValidFlag vf{w.rsz};
     hipLaunchKernelGGL(k_scan_tiles<ValidFlag>, dim3(ntiles), dim3(256), 0, s, vf, nslots, w.tiles);

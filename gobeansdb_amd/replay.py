@@ -405,6 +405,121 @@ def hint_digest(offset, header, vhash, key_base: int = 0, file_id: int = 0) -> i
     return int(np.bitwise_xor.reduce(m))
 
 
+@dataclass
+class ReadResult:
+    """read_records' answer, one entry per request (in request order)."""
+    status: torch.Tensor       # int32 [n] _lib.RD_*: readRecordAt's verdict
+    key_eq: torch.Tensor | None  # uint8 [n] 1 = OK and the record's key is the wanted one; None without keys
+    header: torch.Tensor       # int32 [n, 6]: crc, ts, flag, ver, ksz, vsz as stored (zeros: ALIGN, EOF_HEADER)
+    flag: torch.Tensor         # int32 [n] flag after Payload.Decompress (0 for a failed request)
+    value_len: torch.Tensor    # int32 [n] value length after decompress
+    vhash: torch.Tensor        # int32 [n] Getvhash of the value as delivered (uint16)
+    dec_status: torch.Tensor   # int32 [n] the decoder's status of a compressed record (_lib.OK otherwise)
+    in_out: torch.Tensor       # uint8 [n]: 1 = value in values.data at val_off, 0 = in the chunk at val_off
+    val_off: torch.Tensor      # int64 [n]
+    # the decoder outputs of the OK requests with FLAG_COMPRESS, in request order (as ReplayResult.values)
+    values: batch.BlockBatch
+    data: torch.Tensor         # the chunk read (val_off's base where in_out is 0)
+    # the plan's read-back: (requests with status OK, compressed ones among them, their largest
+    # dsize, bytes of decoder output) -- what sized values.data and the decoder launch
+    totals: tuple[int, int, int, int] = (0, 0, 0, 0)
+
+    @property
+    def n(self) -> int:
+        return int(self.status.numel())
+
+    def value(self, i: int) -> bytes:
+        """Request i's value after Payload.Decompress (the decoded bytes, or the raw body where the
+        record is not compressed or its decode failed); ValueError for a request that failed."""
+        st = int(self.status[i])
+        if st != _lib.RD_OK:
+            raise ValueError(f"request {i} failed: {_lib.RD_NAMES[st]}")
+        o, n = int(self.val_off[i]), int(self.value_len[i])
+        src = self.values.data if int(self.in_out[i]) else self.data
+        return src[o:o + n].cpu().numpy().tobytes()
+
+
+def read_records(data: torch.Tensor, offsets, keys: list[bytes] | None = None, max_key: int = MAX_KEY_LEN,
+                 body_max: int = BODY_MAX, workspace: batch.Workspace | None = None, stream=None) -> ReadResult:
+    """Many records at positions the caller knows, in one pass (a multi-key GET, GC's collision
+    lookups, a hint file's positions): dataChunk.GetRecordByOffset (store/datachunk.go:150-169) for
+    every offset of `offsets` (a sequence, an ndarray or an int64 device tensor) over the chunk
+    `data` in device memory.  qlzx_read_plan checks each request as readRecordAt does (sizes, then
+    the record CRC) and plans the decode of those that passed; the host reads five numbers back
+    once, as replay() does; qlzx_decompress_batch decodes the compressed ones (no CRC arguments:
+    the record CRC was verified before any QuickLZ header was believed); qlzx_read_finish reports
+    per request.  `keys` (optional, one per offset) are compared on the device: key_eq[i] == 0 on
+    an OK request is the caller's hash collision (store/bucket.go:452-498), not an error."""
+    if stream is not None:   # uploads, launches and the read-back all on the caller's stream
+        with torch.cuda.stream(stream):
+            return read_records(data, offsets, keys, max_key, body_max, workspace)
+    L = _lib.lib()
+    dev = data.device
+    ws = workspace or batch.Workspace(dev)
+    st_ = batch._stream()
+    size = int(data.numel())
+    if isinstance(offsets, torch.Tensor):
+        off = offsets.to(device=dev, dtype=torch.int64).contiguous()
+    else:
+        host = np.asarray(offsets)
+        host = host.view(np.int64) if host.dtype == np.uint64 else host.astype(np.int64)
+        off = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).to(dev)
+    n = int(off.numel())
+    cap = max(n, 1)
+    wk = wk_off = wk_len = key_eq = None
+    if keys is not None:
+        if len(keys) != n:
+            raise ValueError("keys: one per offset")
+        koff, _ = batch.pack_offsets([len(k) for k in keys], align=1)
+        wk = torch.from_numpy(np.frombuffer(b"".join(keys) + b"\0", dtype=np.uint8).copy()).to(dev)
+        wk_off = torch.from_numpy(koff.view(np.int64)).to(dev)     # (null pointers when n == 0: not read)
+        wk_len = torch.from_numpy(np.asarray([len(k) for k in keys], dtype=np.int32)).to(dev)
+        key_eq = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if n == 0:
+        off = torch.zeros(1, dtype=torch.int64, device=dev)
+    status = torch.empty(cap, dtype=torch.int32, device=dev)
+    hdr = torch.empty(cap * 6, dtype=torch.int32, device=dev)
+    comp_idx = torch.empty(cap, dtype=torch.int32, device=dev)
+    comp_off = torch.empty(cap, dtype=torch.int64, device=dev)
+    comp_len = torch.empty(cap, dtype=torch.int32, device=dev)
+    comp_dsize = torch.empty(cap, dtype=torch.int32, device=dev)
+    comp_dst = torch.empty(cap, dtype=torch.int64, device=dev)
+    totals = torch.zeros(5, dtype=torch.int32, device=dev)
+    ws_bytes = L.qlzx_read_plan_workspace_size(n)
+    w = ws.get(ws_bytes)
+    _lib.check(L.qlzx_read_plan(data.data_ptr() if size else None, size, off.data_ptr(), n, max_key, body_max,
+                                batch._ptr(wk), batch._ptr(wk_off), batch._ptr(wk_len), status.data_ptr(),
+                                batch._ptr(key_eq), hdr.data_ptr(), comp_idx.data_ptr(), comp_off.data_ptr(),
+                                comp_len.data_ptr(), comp_dsize.data_ptr(), comp_dst.data_ptr(), totals.data_ptr(),
+                                w.data_ptr(), ws_bytes, st_), "qlzx_read_plan")
+    # the one read-back: it sizes the output buffer and the decoder launch
+    t = totals.cpu().numpy().view(np.uint32)
+    ncomp, maxd = int(t[1]), int(t[2])
+    out_bytes = int(t[3]) | (int(t[4]) << 32)
+    out = torch.empty(out_bytes + 64, dtype=torch.uint8, device=dev)
+    cst = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
+    cds = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
+    values = batch.BlockBatch(out, comp_dst[:ncomp], comp_dsize[:ncomp])
+    if ncomp:
+        csrc = batch.BlockBatch(data, comp_off[:ncomp], comp_len[:ncomp])
+        cds, cst, _ = batch.decompress(csrc, values, dst_cap=comp_dsize[:ncomp], max_dsize=maxd, workspace=ws)
+    flag = torch.empty(cap, dtype=torch.int32, device=dev)
+    value_len = torch.empty(cap, dtype=torch.int32, device=dev)
+    in_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    val_off = torch.empty(cap, dtype=torch.int64, device=dev)
+    vh16 = torch.empty(cap, dtype=torch.int16, device=dev)
+    dec = torch.empty(cap, dtype=torch.int32, device=dev)
+    _lib.check(L.qlzx_read_finish(data.data_ptr() if size else None, off.data_ptr(), n, status.data_ptr(),
+                                  totals.data_ptr(), comp_idx.data_ptr(), cst.data_ptr(), cds.data_ptr(),
+                                  comp_dst.data_ptr(), out.data_ptr(), flag.data_ptr(), value_len.data_ptr(),
+                                  in_out.data_ptr(), val_off.data_ptr(), vh16.data_ptr(), dec.data_ptr(), st_),
+               "qlzx_read_finish")
+    vh = vh16[:n].to(torch.int32) & 0xFFFF
+    return ReadResult(status[:n], None if key_eq is None else key_eq[:n], hdr[: 6 * n].view(n, 6), flag[:n],
+                      value_len[:n], vh, dec[:n], in_out[:n], val_off[:n], values, data,
+                      (int(t[0]), ncomp, maxd, out_bytes))
+
+
 def read_record(rec: bytes) -> tuple[int, bytes] | None:
     """One record as a GET reads it: readRecordAt's CRC check (store/datafile.go:161-168) and
     Payload.Decompress (store/item.go:163-176) -- header[4:24] and the key through crc32_write

@@ -240,6 +240,66 @@ int qlzx_replay_finish(const uint8_t *data, const uint64_t *rec_off, const uint3
                        const uint64_t *comp_dst_off, const uint8_t *outbuf, uint32_t cap, int32_t *flag,
                        int32_t *value_len, uint8_t *in_out, uint64_t *val_off, uint16_t *vhash, void *stream);
 
+/* ---- batched record reads at known offsets (a multi-GET) ----
+ * Replaces a loop of dataChunk.GetRecordByOffset (store/datachunk.go:150-169: readRecordAt,
+ * store/datafile.go:114-170, then Payload.Decompress, store/item.go:163-176) over one chunk file
+ * resident in device memory: Bucket.get -> GetRecordByPos per key of a memcache "get k1 k2 ..."
+ * (store/bucket.go:405-499), GC's collision lookups (store/gc.go:300), anything driven by a hint
+ * file.  Request i reads the record at rec_off[i]; requests are independent and may repeat.
+ * Same shape as the replay: plan, read totals[5] back, qlzx_decompress_batch over the ncomp
+ * compressed records (dst_cap = comp_dsize, no CRC arguments: the record CRC is verified in the
+ * plan, before any QuickLZ header is believed), finish.  Nothing allocates; every launch goes on
+ * `stream`.
+ * enum qlzx_read_status: readRecordAt's checks in its order, the first failure is the verdict --
+ *   ALIGN       rec_off % 256 != 0 (positions carry offsets in units of 256, store/leaf.go:56-65)
+ *   EOF_HEADER  rec_off + 24 > size                 (store/datafile.go:123)
+ *   KEY_SIZE    ksz == 0 || ksz > max_key           (:129, config/mc_config.go:33-35)
+ *   VALUE_SIZE  vsz > body_max                      (:133)
+ *   EOF_BODY    rec_off + 24 + ksz + vsz > size     (:149)
+ *   CRC         ~crc(header[4:24] ‖ key ‖ value) != header[0:4]   (:161-168) */
+enum qlzx_read_status {
+    QLZX_RD_OK = 0,
+    QLZX_RD_ALIGN,
+    QLZX_RD_EOF_HEADER,
+    QLZX_RD_KEY_SIZE,
+    QLZX_RD_VALUE_SIZE,
+    QLZX_RD_EOF_BODY,
+    QLZX_RD_CRC
+};
+/* Workspace of qlzx_read_plan for n requests. */
+size_t qlzx_read_plan_workspace_size(uint32_t n);
+/* readRecordAt for every request, and the decode plan of those that passed.
+ *   max_key / body_max: MaxKeyLen and BodyMax as in qlzx_replay_index (24 + max_key + body_max
+ *   must stay below 4 GiB); size / 256 < 0xfffffff0.
+ *   want_key / want_key_off / want_key_len (all three or none): the key the caller expects at
+ *   request i, want_key[want_key_off[i] ..+ want_key_len[i]).  key_eq[i] (nullable iff no keys)
+ *   = 1 iff rd_status[i] is OK and the record's key equals it (bytes.Compare,
+ *   store/bucket.go:442).  A mismatch is not an error: the record is delivered and decoded, as
+ *   the reference reads it before comparing (store/bucket.go:452-498 is the caller's part).
+ *   rd_status[i]: enum qlzx_read_status.  hdr[6 i ..]: the stored header (crc, ts, flag, ver,
+ *   ksz, vsz); zeros for ALIGN and EOF_HEADER.
+ *   comp_*: as qlzx_replay_plan's, over the OK requests with FLAG_COMPRESS in request order
+ *   (comp_idx = request index); capacity n each.
+ *   totals[5] = {requests with rd_status OK, ncomp, max dsize, output bytes (lo, hi)}.
+ * n == 0 zeroes totals and returns QLZX_R_OK. */
+int qlzx_read_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, uint32_t n, uint32_t max_key,
+                   uint64_t body_max, const uint8_t *want_key, const uint64_t *want_key_off,
+                   const uint32_t *want_key_len, int32_t *rd_status, uint8_t *key_eq, int32_t *hdr,
+                   uint32_t *comp_idx, uint64_t *comp_off, uint32_t *comp_len, uint32_t *comp_dsize,
+                   uint64_t *comp_dst_off, uint32_t *totals, void *workspace, size_t workspace_bytes, void *stream);
+/* Payload.Decompress's outcome per request (store/item.go:163-176), after qlzx_decompress_batch
+ * (comp_status, comp_dsize = its outputs).  OK requests, as qlzx_replay_finish: flag
+ * (FLAG_COMPRESS cleared only when the value decoded), value_len, in_out / val_off (1: outbuf +
+ * val_off, 0: data + val_off; a failed decode keeps the raw body and the flag, :167-170) and
+ * Getvhash of the value as delivered.  dec_status[i]: the decoder's enum qlzx_status for a
+ * compressed record (the error the reference only logs), QLZX_OK otherwise.  Failed requests get
+ * flag = value_len = in_out = val_off = vhash = 0.  n == 0 returns QLZX_R_OK. */
+int qlzx_read_finish(const uint8_t *data, const uint64_t *rec_off, uint32_t n, const int32_t *rd_status,
+                     const uint32_t *totals, const uint32_t *comp_idx, const int32_t *comp_status,
+                     const uint32_t *comp_dsize, const uint64_t *comp_dst_off, const uint8_t *outbuf,
+                     int32_t *flag, int32_t *value_len, uint8_t *in_out, uint64_t *val_off, uint16_t *vhash,
+                     int32_t *dec_status, void *stream);
+
 /* Getvhash (store/item.go:89-100, Fnv1a of utils/hash.go:8-16) of n values. */
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,
                      void *stream);

@@ -1,0 +1,332 @@
+"""GPU batched record reads at known offsets (replay.read_records: qlzx_read_plan,
+qlzx_decompress_batch, qlzx_read_finish) against oracle/replay.py's readRecordAt, Getvhash and
+the oracle decoder.  The expected error kind restates the order of store/datafile.go:114-170."""
+import random
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from oracle import replay as R
+
+pytestmark = pytest.mark.gpu
+
+OK, ALIGN, EOF_HEADER, KEY_SIZE, VALUE_SIZE, EOF_BODY, CRC = range(7)
+ZERO_HDR = (0,) * 6
+
+
+def _expect(data: bytes, off: int, max_key=R.MAX_KEY_LEN, body_max=R.BODY_MAX):
+    """(status, stored header, flag, value, vhash, decode ok) of one request: readRecordAt's checks in
+    its order, then Payload.Decompress with the error swallowed."""
+    size = len(data)
+    if off % 256:
+        return ALIGN, ZERO_HDR, 0, None, 0, True
+    if off + 24 > size:
+        return EOF_HEADER, ZERO_HDR, 0, None, 0, True
+    hdr = struct.unpack_from("<6i", data, off)
+    ksz, vsz = struct.unpack_from("<II", data, off + 16)
+    st = OK
+    if ksz == 0 or ksz > max_key:
+        st = KEY_SIZE
+    elif vsz > body_max:
+        st = VALUE_SIZE
+    elif off + 24 + ksz + vsz > size:
+        st = EOF_BODY
+    rec = R.read_record_at(data, off, max_key, body_max) if st == OK else None
+    if rec is None:
+        return (CRC if st == OK else st), hdr, 0, None, 0, True
+    flag, body, dec_ok = rec.flag, rec.body, True
+    if flag & R.FLAG_COMPRESS:
+        dst, out = O.decompress(body)
+        dec_ok = dst == O.OK
+        if dec_ok:
+            flag, body = flag - R.FLAG_COMPRESS, out
+    return OK, hdr, flag, body, R.getvhash(body), dec_ok
+
+
+def _dev(data: bytes):
+    return torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda() if data else \
+        torch.zeros(0, dtype=torch.uint8, device="cuda")
+
+
+def _read(data: bytes, offsets, keys=None, **kw):
+    """read_records, pulled to the host once: (result, rows) with a row per request
+    (status, header, flag, value | None, vhash, decode ok)."""
+    from gobeansdb_amd import replay
+    res = replay.read_records(_dev(data), offsets, keys=keys, **kw)
+    torch.cuda.synchronize()
+    st = res.status.cpu().numpy()
+    hdr = res.header.cpu().numpy()
+    flag = res.flag.cpu().numpy().view(np.uint32)
+    vlen = res.value_len.cpu().numpy()
+    vh = res.vhash.cpu().numpy()
+    dec = res.dec_status.cpu().numpy()
+    io = res.in_out.cpu().numpy()
+    voff = res.val_off.cpu().numpy()
+    outbuf = res.values.data.cpu().numpy()
+    rows = []
+    for i in range(res.n):
+        val = None
+        if st[i] == OK:
+            o, n = int(voff[i]), int(vlen[i])
+            val = outbuf[o:o + n].tobytes() if io[i] else data[o:o + n]
+        else:
+            assert (int(flag[i]), int(vlen[i]), int(io[i]), int(voff[i]), int(vh[i]), int(dec[i])) == (0,) * 6
+        rows.append((int(st[i]), tuple(int(x) for x in hdr[i]), int(flag[i]), val, int(vh[i]), int(dec[i]) == 0))
+    return res, rows
+
+
+def _check(data: bytes, offsets, **kw):
+    lim = {k: v for k, v in kw.items() if k in ("max_key", "body_max")}
+    res, rows = _read(data, offsets, **kw)
+    assert len(rows) == len(offsets)
+    for i, off in enumerate(offsets):
+        assert rows[i] == _expect(data, int(off), **lim), (i, off)
+    nok = sum(r[0] == OK for r in rows)
+    ncomp = sum(r[0] == OK and bool(r[1][2] & R.FLAG_COMPRESS) for r in rows)
+    assert res.totals[:2] == (nok, ncomp) and res.values.n == ncomp
+    return res, rows
+
+
+def _random_file(rng: random.Random, nrec: int):
+    out = b""
+    for i in range(nrec):
+        n = int(np.exp(rng.uniform(np.log(5), np.log(40000))))
+        val = O.gen_text(rng.getrandbits(32), i, n) if rng.random() < 0.7 else O.gen_image(rng.getrandbits(32), i, n)
+        key = b"key_%016x" % rng.getrandbits(64)
+        flag = 0
+        if n > 256 and rng.random() < 0.6:
+            c = O.compress(val)
+            if len(c) < 0.9 * n:
+                val, flag = c, R.FLAG_COMPRESS
+        out += R.make_record(key, val, flag=flag, ver=rng.randrange(-3, 100), ts=rng.getrandbits(32))
+    return out
+
+
+def _offsets(data: bytes):
+    recs, _ = R.stream_all(data)
+    return [r.offset for r in recs]
+
+
+@pytest.fixture(scope="module")
+def rfile():
+    data = _random_file(random.Random(7), 60)
+    return data, _offsets(data)
+
+
+def test_golden_chunk(cuda, golden):
+    data = golden.records_data
+    want = {row[0]: row for row in R.replay(data)[0]}
+    offs = _offsets(data)
+    assert sorted(offs) == sorted(want)
+    random.Random(1).shuffle(offs)
+    res, rows = _read(data, offs)
+    for off, (st, hdr, flag, val, vh, _) in zip(offs, rows):
+        _, _, key, ver, wflag, wval, wvh = want[off]
+        assert st == OK and hdr == struct.unpack_from("<6i", data, off)
+        assert (hdr[3], data[off + 24: off + 24 + hdr[4]]) == (ver, key)
+        assert (flag, val, vh) == (wflag, wval, wvh), off
+    for i in range(0, len(offs), max(1, len(offs) // 8)):   # the accessor reads the same bytes
+        assert res.value(i) == rows[i][3]
+
+
+def test_random_file_every_slot(cuda, rfile):
+    data, recs = rfile
+    size = len(data)
+    assert len(recs) == 60
+    other = sorted(set(range(0, size, 256)) - set(recs))
+    assert other
+    dup = next(o for o in recs if struct.unpack_from("<I", data, o + 8)[0] & R.FLAG_COMPRESS)
+    offs = recs + other + [dup, size - 10, size, size + 256, recs[3] + 4]
+    random.Random(2).shuffle(offs)
+    res, rows = _check(data, offs)
+    assert {r[0] for r in rows} >= {OK, ALIGN, EOF_HEADER}
+    a, b = [i for i, o in enumerate(offs) if o == dup]
+    assert rows[a] == rows[b] and rows[a][0] == OK
+    assert int(res.in_out[a]) == int(res.in_out[b]) == 1      # decoded twice, into two places
+    assert int(res.val_off[a]) != int(res.val_off[b])
+    with pytest.raises(ValueError):
+        res.value(offs.index(size))
+
+
+def test_duplicates_of_a_compressed_record_decode_apart(cuda):
+    text = O.gen_text(3, 0, 3000)
+    data = R.make_record(b"k", O.compress(text), flag=R.FLAG_COMPRESS)
+    res, rows = _check(data, [0, 0])
+    assert rows[0][3] == rows[1][3] == text
+    assert int(res.in_out[0]) == int(res.in_out[1]) == 1 and int(res.val_off[0]) != int(res.val_off[1])
+
+
+def test_counts_that_cross_code_paths(cuda):
+    rng = random.Random(5)
+    recs = []
+    for i in range(1500):   # crosses the 1024-element scan tile, compressed and raw interleaved
+        n = rng.randrange(0, 301)
+        val, flag = O.gen_text(9, i, n), 0
+        if n and rng.random() < 0.5:
+            val, flag = O.compress(val), R.FLAG_COMPRESS
+        recs.append(R.make_record(b"t%05d" % i, val, flag=flag, ver=i))
+    data = b"".join(recs)
+    offs = _offsets(data)
+    assert len(offs) == 1500
+    res, _ = _check(data, [])
+    assert res.n == 0 and res.totals == (0, 0, 0, 0) and res.key_eq is None
+    assert _read(data, [], keys=[])[0].key_eq.numel() == 0
+    _check(data, offs[7:8])
+    _check(data, offs[100:165])
+    _check(data, np.asarray(offs, dtype=np.int64))
+    rng.shuffle(offs)
+    res, rows = _check(data, torch.tensor(offs, dtype=torch.int64, device="cuda"))
+    assert res.totals[0] == 1500 and 500 < res.totals[1] < 1000
+
+
+def test_crc_spans_and_small_bodies(cuda):
+    rng = np.random.default_rng(3)
+    key = b"span_key"
+    recs = [R.make_record(key, rng.integers(0, 256, span - 20 - len(key), dtype=np.uint8).tobytes(), ver=span)
+            for span in (4095, 4096, 4097, 8193)]                      # wave_crc's 4 KiB stripes
+    recs.append(R.make_record(b"empty", b""))                          # vsz = 0
+    recs.append(R.make_record(b"two", b"\x4f\x00", flag=R.FLAG_COMPRESS))  # shorter than a QuickLZ header
+    data = b"".join(recs)
+    offs = _offsets(data)
+    assert len(offs) == 6
+    res, rows = _check(data, offs)
+    assert [r[0] for r in rows] == [OK] * 6
+    assert rows[4][3] == b"" and rows[4][4] == R.getvhash(b"")
+    st, hdr, flag, val, vh, dec_ok = rows[5]   # decode fails: the flag stays, the value is the raw body
+    assert flag & R.FLAG_COMPRESS and val == b"\x4f\x00" and not dec_ok and int(res.in_out[5]) == 0
+
+
+def test_long_records(cuda):
+    """A CRC span over 128 KiB goes to the segmented long-CRC kernel, a dsize over 64 KiB to the
+    whole-GPU decoder."""
+    rng = np.random.default_rng(4)
+    raw = rng.integers(0, 256, 300 << 10, dtype=np.uint8).tobytes()
+    img = O.gen_image(8, 1, 200 << 10)
+    comp = O.compress(img)
+    assert len(comp) > (128 << 10)
+    bad = bytearray(R.make_record(b"raw300_bad", raw))
+    bad[24 + 10 + (150 << 10)] ^= 0x20
+    data = R.make_record(b"raw300", raw) + R.make_record(b"img200", comp, flag=R.FLAG_COMPRESS) + bytes(bad)
+    offs = _offsets(data) + [len(data) - len(bad)]
+    assert len(offs) == 3
+    res, rows = _check(data, offs, keys=[b"raw300", b"img2oo", b"raw300_bad"])
+    assert [r[0] for r in rows] == [OK, OK, CRC]
+    assert rows[0][3] == raw and rows[1][3] == img
+    assert res.key_eq.cpu().tolist() == [1, 0, 0]
+
+
+def _tail_cut_chunk():
+    body = O.gen_text(2, 0, 700)
+    last = R.make_record(b"last", body)[: 24 + 4 + len(body)]          # no padding: ends at `size`
+    head = R.make_record(b"first", b"abc") + R.make_record(b"second", O.compress(body), flag=R.FLAG_COMPRESS)
+    return head + last, [0, 256, len(head)]
+
+
+def test_boundary_verdicts(cuda):
+    data, offs = _tail_cut_chunk()
+    assert len(data) % 256 != 0
+    assert [r[0] for r in _check(data, offs)[1]] == [OK, OK, OK]
+    assert [r[0] for r in _check(data[:-1], offs)[1]] == [OK, OK, EOF_BODY]
+    assert [r[0] for r in _check(data[: offs[2] + 24], offs)[1]] == [OK, OK, EOF_BODY]
+    assert [r[0] for r in _check(data[: offs[2] + 23], offs)[1]] == [OK, OK, EOF_HEADER]
+    assert [r[0] for r in _check(data[: offs[2] + 1], offs)[1]] == [OK, OK, EOF_HEADER]
+
+    def crafted(ksz, vsz):
+        return (struct.pack("<IIiiII", 0x12345678, 1, 0, 2, ksz, vsz) + b"k" * 40).ljust(256, b"\0")
+    lim = dict(max_key=30, body_max=8192)
+    chunk = crafted(0, 10) + crafted(31, 10) + crafted(5, 8193) + crafted(31, 8193) + crafted(0, 1 << 31) + \
+        R.make_record(b"k" * 30, bytes(8192)) + crafted(30, 8192)
+    offs = list(range(0, 6 * 256, 256)) + [len(chunk) - 256]
+    _, rows = _check(chunk, offs, **lim)
+    assert [r[0] for r in rows] == [KEY_SIZE, KEY_SIZE, VALUE_SIZE, KEY_SIZE, KEY_SIZE, OK, EOF_BODY]
+    assert rows[2][1][4:] == (5, 8193)   # the stored header comes back with the verdict
+
+
+def test_corruption(cuda, rfile):
+    data, recs = rfile
+    d = bytearray(data)
+    hit = {}
+    for name, k, where in (("key", 5, 24 + 3), ("value", 11, 24 + 20 + 2), ("ts", 23, 4), ("flag", 31, 9),
+                           ("crc", 42, 1)):
+        d[recs[k] + where] ^= 0x40
+        hit[recs[k]] = name
+    kbad = len(d)
+    d += R.make_record(b"kbad", b"\x4f" + bytes(40), flag=R.FLAG_COMPRESS)   # CRC recomputed: found, decode swallowed
+    data2 = bytes(d)
+    offs = recs + [kbad]
+    res, rows = _check(data2, offs)
+    assert [o for o, r in zip(offs, rows) if r[0] == CRC] == sorted(hit)
+    assert all(r[0] == OK for o, r in zip(offs, rows) if o not in hit)
+    _, clean = _read(data, recs)
+    for o, r, c in zip(recs, rows, clean):
+        if o not in hit:
+            assert r == c
+    st, hdr, flag, val, vh, dec_ok = rows[-1]
+    assert st == OK and flag & R.FLAG_COMPRESS and val == b"\x4f" + bytes(40) and not dec_ok
+
+
+def test_crc_before_plan(cuda):
+    """A body that fails the record CRC never reaches the plan: its QuickLZ header (here claiming
+    40 MiB) sizes nothing."""
+    texts = [O.gen_text(6, i, n) for i, n in enumerate((900, 5000, 2500, 7000))]
+    recs = [R.make_record(b"c%d" % i, O.compress(t), flag=R.FLAG_COMPRESS) for i, t in enumerate(texts)]
+    recs.insert(2, R.make_record(b"raw", b"plain value"))
+    offs = [sum(len(r) for r in recs[:i]) for i in range(len(recs))]
+    d = bytearray(b"".join(recs))
+    liar = offs[1] + 24 + 2
+    assert d[liar] & 2                               # the 9-byte QuickLZ header: dsize at bytes 5..8
+    d[liar + 5: liar + 9] = struct.pack("<I", 40 << 20)
+    data = bytes(d)
+    res, rows = _check(data, offs)
+    assert [r[0] for r in rows] == [OK, CRC, OK, OK, OK]
+    without, _ = _check(data, offs[:1] + offs[2:])
+    assert res.totals == without.totals
+    assert res.totals[0] == 4 and res.totals[1] == 3 and res.totals[2] == 7000
+    assert res.values.data.numel() == without.values.data.numel() < (1 << 20)
+
+
+def test_keys(cuda, rfile):
+    data, recs = rfile
+    keys = [R.read_record_at(data, o).key for o in recs]
+    offs = recs + [recs[0] + 256 if recs[0] + 256 not in recs else recs[0] + 4, len(data)]
+    want = keys + [b"anything", b""]
+    want[4] = bytes([want[4][0] ^ 1]) + want[4][1:]   # same length, different
+    want[9] = want[9][:-1]                            # a proper prefix
+    want[13] = want[13] + b"x"                        # the right key plus one byte
+    want[20] = b""
+    res, rows = _check(data, offs, keys=want)
+    eq = res.key_eq.cpu().tolist()
+    bad = {4, 9, 13, 20, len(recs), len(recs) + 1}
+    assert eq == [0 if i in bad else 1 for i in range(len(offs))]
+    assert all(rows[i][0] == OK and rows[i][3] is not None for i in (4, 9, 13, 20))   # still delivered
+    assert rows[-1][0] == EOF_HEADER and rows[-2][0] != OK
+    assert _read(data, recs)[0].key_eq is None
+    with pytest.raises(ValueError):
+        _read(data, recs, keys=keys[:-1])
+
+
+def test_agrees_with_replay_and_read_record(cuda):
+    from gobeansdb_amd import replay
+    data = _random_file(random.Random(21), 40)
+    t = _dev(data)
+    rp = replay.replay(t)
+    rd = replay.read_records(t, rp.offset)
+    torch.cuda.synchronize()
+    assert rd.n == rp.n == 40 and int((rd.status != 0).sum()) == 0
+    for a, b in ((rd.header, rp.header), (rd.flag, rp.flag), (rd.value_len, rp.value_len), (rd.vhash, rp.vhash)):
+        assert torch.equal(a, b)
+    offs = rp.offset.cpu().tolist()
+    for j in range(rp.n):
+        assert rd.value(j) == rp.value(j)
+    side = torch.cuda.Stream()   # the same call on a stream of the caller's
+    on_side = replay.read_records(t, offs, keys=[b"x"] * rp.n, stream=side)
+    side.synchronize()
+    assert torch.equal(on_side.vhash, rd.vhash) and torch.equal(on_side.val_off, rd.val_off)
+    assert int(on_side.key_eq.sum()) == 0 and [on_side.value(j) for j in (0, 39)] == [rd.value(0), rd.value(39)]
+    for j in range(0, 40, 5):
+        ksz, vsz = int(rd.header[j, 4]), int(rd.header[j, 5])
+        one = replay.read_record(data[offs[j]: offs[j] + 24 + ksz + vsz])
+        assert one == (int(rd.flag[j]), rd.value(j))
