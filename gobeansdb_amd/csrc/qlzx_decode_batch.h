@@ -31,7 +31,7 @@ struct GroupRec {
 
 constexpr int32_t kPending = -1;  // status of blocks left to the general path
 constexpr uint32_t kBlkSkip = 0, kBlkStored = 1, kBlkCompressed = 2;
-// K1 workgroup: one wave (the 16 KiB LDS ring per wave bounds occupancy)
+// K1 workgroup: one wave (the 8 KiB LDS ring per wave bounds occupancy)
 constexpr uint32_t kParseWG = 64;
 #ifndef QLZX_CHUNK_BLOCKS  // blocks per K1/K2 chunk for batches of values up to 16 KiB
 #define QLZX_CHUNK_BLOCKS 262144
@@ -172,6 +172,13 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
+// Lane masks: the lanes where a < b (unsigned) or a != b, as the compare itself leaves them in an
+// SGPR pair, and the lane's own bit of a wave-uniform mask as a bool (no instruction).
+constexpr int kIcmpNe = 33, kIcmpUlt = 36;  // LLVM's integer compare predicates
+__device__ __forceinline__ uint64_t cmp_lt(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, kIcmpUlt); }
+__device__ __forceinline__ uint64_t cmp_ne(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, kIcmpNe); }
+__device__ __forceinline__ bool in_mask(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+
 __device__ __forceinline__ uint32_t ff1_or(uint64_t m, uint32_t dflt) {
     return m ? (uint32_t)__builtin_ctzll(m) : dflt;
 }
@@ -188,7 +195,7 @@ __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
 }
 // Value of lane - 1 (0 in lane 0): DPP wave_shr:1.
 __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
 }
 
 }  // namespace qlzx

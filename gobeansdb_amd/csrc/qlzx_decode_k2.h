@@ -88,7 +88,11 @@ __device__ __forceinline__ void dec_v4_block(K2v4Lds<WIN> &L, const uint8_t *src
     PROF_DECL
     uint32_t D = 0, bt = 0, c = 0, cin = 0;
     bool tail = false, complete = false, err = false;
-    bool pend = false, mp = false;  // some lane's item / this lane's item waits for its marker slot
+    // Per-lane predicates that also decide a wave-wide branch are kept as lane masks: cmp_lt and
+    // its kin give a compare's mask in an SGPR pair, the masks are joined on the scalar unit and
+    // in_mask() hands a mask back as the lane's bool for free.  A ballot of a bool that another
+    // basic block computed costs a select and a compare on the vector unit, three times a batch.
+    uint64_t pendm = 0;  // lanes whose item waits for its marker slot
     uint32_t pd = 0, pkey = 0;
     uint32_t plit = 0;
 
@@ -96,15 +100,15 @@ __device__ __forceinline__ void dec_v4_block(K2v4Lds<WIN> &L, const uint8_t *src
     // (posm_n, tok_n) and the GroupRec after it into gr_nn
     auto batch = [&](uint32_t posm, uint32_t tok, const GroupRec &gr_next, uint32_t &posm_n, uint32_t &tok_n,
                      GroupRec &gr_nn) __attribute__((always_inline)) {
-        if (pend) {  // a straddling batch's items not marked by a chunk yet (all start below c + CH)
-            const bool wr = mp;
-            if (wr) {
+        if (pendm) {  // a straddling batch's items not marked by a chunk yet (all start below c + CH)
+            if (in_mask(pendm)) {
                 L.mk[pd & (MR - 1)] = pkey;
                 if (plit < 0x100u) L.win[pd & (W - 1)] = (uint8_t)plit;
             }
-            pend = mp = false;
+            pendm = 0;
         }
-        const bool v = bt * 64 + lane < nitems;
+        const uint64_t vm = cmp_lt(lane, nitems - bt * 64);  // bt < nb: the difference is positive
+        const bool v = in_mask(vm);
         {
             uint32_t tp;
             posm_n = tok_pos(gr_next, ck, tp);
@@ -112,45 +116,47 @@ __device__ __forceinline__ void dec_v4_block(K2v4Lds<WIN> &L, const uint8_t *src
             ck.next();
             gr_nn = rb[min(ck.g, glast)];
         }
-        const bool ism = v && (posm >> 31) != 0;
+        const uint64_t ismm = vm & cmp_ne(posm >> 31, 0u);
+        const bool ism = in_mask(ismm);
         const uint32_t pos = posm & 0x7fffffffu;
-        const uint32_t t = tok >> (8 * (pos - min(pos, csize - 4)));  // the last tokens: dword clamped
+        // the last tokens: dword clamped, so the token starts pos - (csize - 4) bytes into it
+        const uint32_t t = __builtin_amdgcn_alignbyte(0u, tok, __builtin_elementwise_sub_sat(pos, csize - 4));
         uint32_t off, mlen, tl;
         decode_tok_bf(t, off, mlen, tl);
         const uint32_t len = ism ? mlen : (v ? 1u : 0u);
         const uint32_t incl = wave_incl_scan(len);
         const uint32_t total = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_readlane(incl, 63));
         const uint32_t d = D + incl - len;
-        const bool live = v && d < dsize;
-        bool bad, last = false;
+        const uint64_t livem = vm & cmp_lt(d, dsize);
+        const bool live = in_mask(livem);
+        uint64_t badm;
         if (tail || D + total > tail_from) {
             tl = ism ? tl : 1u;
             const uint64_t tail_lanes = __ballot(live && !ism && d >= tail_from);
             const uint32_t tail_lane = tail ? 0u : ff1_or(tail_lanes, 64u);  // C4: no match after it
             tail = tail || tail_lanes != 0;
             const bool mok = off >= 3 && off <= d && d + len + 4 <= dsize && lane < tail_lane;  // C3, C4
-            last = live && d + len == dsize;  // C5: the item completing dsize ends the stream
+            const bool last = live && d + len == dsize;  // C5: the item completing dsize ends the stream
             const uint32_t ip_end = pos + tl;
             const bool eok = ip_end == csize || (ip_end < hdr + 9 && csize == hdr + 9);
-            bad = live && ((ism && !mok) || (last && !eok));
+            badm = __ballot(live && ((ism && !mok) || (last && !eok)));
+            complete = __ballot(last) != 0;
         } else {
-            bad = ism && (off < 3 || off > d);  // C3
+            badm = ismm & (cmp_lt(off, 3u) | cmp_lt(d, off));  // C3
         }
-        if (__ballot(bad)) {
+        if (badm) {
             err = true;
             return;
         }
-        complete = __ballot(last) != 0;
         const uint32_t key = (d << 16) | (ism ? off : 0u);
-        const bool wr = live && d < c + MR;
-        if (wr) {
+        const uint64_t wrm = livem & cmp_lt(d, c + MR);
+        if (in_mask(wrm)) {
             L.mk[d & (MR - 1)] = key;
             // a match's own window slot holds a byte older than the far bound (d < c + MR) that no
             // gather reads before the chunk of d overwrites it: the byte can go there unconditionally
             L.win[d & (W - 1)] = (uint8_t)t;
         }
-        mp = live && !wr;
-        pend = __ballot(mp) != 0;
+        pendm = livem & ~wrm;
         pd = d;
         pkey = key;
         plit = ism ? 0x100u : (t & 0xffu);
@@ -162,14 +168,13 @@ __device__ __forceinline__ void dec_v4_block(K2v4Lds<WIN> &L, const uint8_t *src
     // chunk phases while every item starting below c + 256 is known; true when the block is done
     auto chunks = [&]() __attribute__((always_inline)) -> bool {
         while (c < dsize && (complete || D >= c + CH)) {
-            if (pend) {  // items of the last batch that start at or above c_prev + MR
-                const bool wr = mp && pd < c + MR;
-                if (wr) {
+            if (pendm) {  // items of the last batch that start at or above c_prev + MR
+                const uint64_t wrm = pendm & cmp_lt(pd, c + MR);
+                if (in_mask(wrm)) {
                     L.mk[pd & (MR - 1)] = pkey;
                     if (plit < 0x100u) L.win[pd & (W - 1)] = (uint8_t)plit;
                 }
-                mp = mp && !wr;
-                pend = __ballot(mp) != 0;
+                pendm &= ~wrm;
             }
             constexpr uint32_t B = kV4Bpl;
             const uint32_t r0 = B * lane, p0 = c + r0;
