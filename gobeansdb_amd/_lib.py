@@ -24,6 +24,14 @@ STATUS_NAMES = ["OK", "E_SIZE_COMPRESSED", "E_CORRUPT", "E_LEVEL", "E_DST_CAP", 
 # enum qlzx_read_status (qlzx_read_plan's verdict per request)
 RD_OK, RD_ALIGN, RD_EOF_HEADER, RD_KEY_SIZE, RD_VALUE_SIZE, RD_EOF_BODY, RD_CRC = range(7)
 RD_NAMES = ["RD_OK", "RD_ALIGN", "RD_EOF_HEADER", "RD_KEY_SIZE", "RD_VALUE_SIZE", "RD_EOF_BODY", "RD_CRC"]
+# enum qlzx_write_status (qlzx_write_plan / qlzx_write_finish's verdict per record)
+WR_OK, WR_KEY_SIZE, WR_VALUE_SIZE, WR_NO_SPACE = range(4)
+WR_NAMES = ["WR_OK", "WR_KEY_SIZE", "WR_VALUE_SIZE", "WR_NO_SPACE"]
+# QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
+# order, and one for every other answer
+NC_AUDIO_BASIC, NC_AUDIO_AIFF, NC_AUDIO_MPEG, NC_APPLICATION_OGG, NC_AUDIO_MIDI, NC_VIDEO_AVI, NC_AUDIO_WAVE, \
+    NC_OTHER = (1 << k for k in range(8))
+NC_DEFAULT = NC_AUDIO_MPEG | NC_AUDIO_WAVE
 # enum qlzx_return
 R_OK, R_BAD_ARG, R_WORKSPACE, R_HIP, R_NO_DEVICE = 0, -1, -2, -3, -4
 
@@ -118,6 +126,14 @@ def lib() -> ctypes.CDLL:
     L.qlzx_read_plan.restype = ctypes.c_int
     L.qlzx_read_finish.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.qlzx_read_finish.restype = ctypes.c_int
+    L.qlzx_write_plan_workspace_size.argtypes = [u32]
+    L.qlzx_write_plan_workspace_size.restype = sz
+    L.qlzx_write_plan.argtypes = [vp] * 6 + [u32, u32, u64, u32] + [vp] * 7 + [sz, vp]
+    L.qlzx_write_plan.restype = ctypes.c_int
+    L.qlzx_write_decide.argtypes = [vp, vp, u32] + [vp] * 12 + [sz, vp]
+    L.qlzx_write_decide.restype = ctypes.c_int
+    L.qlzx_write_finish.argtypes = [vp] * 9 + [u32] + [vp] * 16 + [u64] + [vp] * 8 + [sz, vp]
+    L.qlzx_write_finish.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

@@ -27,6 +27,7 @@
 #include "qlzx_encode_huge.hip"
 #include "qlzx_replay.hip"
 #include "qlzx_read.hip"
+#include "qlzx_write.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -352,6 +353,81 @@ int qlzx_read_finish(const uint8_t *data, const uint64_t *rec_off, uint32_t n, c
                                            comp_dst_off, outbuf, flag, value_len, in_out, val_off, vhash, dec_status,
                                            (hipStream_t)stream);
     if (e) return fail(QLZX_R_HIP, "qlzx_read_finish", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+size_t qlzx_write_plan_workspace_size(uint32_t n) { return qlzx::write_ws_layout(n, nullptr, nullptr); }
+
+int qlzx_write_plan(const uint8_t *values, const uint64_t *val_off, const uint32_t *val_len, const uint32_t *key_len,
+                    const uint32_t *flag, const int32_t *ver, uint32_t n, uint32_t max_key, uint64_t body_max,
+                    uint32_t not_compress, int32_t *wr_status, uint32_t *try_idx, uint64_t *try_off,
+                    uint32_t *try_len, uint64_t *try_dst_off, uint32_t *totals, void *workspace,
+                    size_t workspace_bytes, void *stream) {
+    if (!totals) return fail(QLZX_R_BAD_ARG, "qlzx_write_plan: null totals");
+    if (n) {
+        if (!values || !val_off || !val_len || !key_len || !flag || !ver || !wr_status || !try_idx || !try_off ||
+            !try_len || !try_dst_off)
+            return fail(QLZX_R_BAD_ARG, "qlzx_write_plan: null arg");
+        if (body_max > 0xffffffffull - 24 - 9 - 256 - max_key)
+            return fail(QLZX_R_BAD_ARG, "qlzx_write_plan: 24 + max_key + body_max + 9 + 256 is 4 GiB or more");
+        if (!workspace || workspace_bytes < qlzx_write_plan_workspace_size(n))
+            return fail(QLZX_R_WORKSPACE, "qlzx_write_plan: workspace too small");
+    }
+    const int e = qlzx::launch_write_plan(values, val_off, val_len, key_len, flag, ver, n, max_key, body_max,
+                                          not_compress, wr_status, try_idx, try_off, try_len, try_dst_off, totals,
+                                          workspace, (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_write_plan", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+int qlzx_write_decide(const uint64_t *val_off, const uint32_t *val_len, uint32_t n, const uint32_t *totals,
+                      const uint32_t *try_idx, const uint32_t *try_len, const uint32_t *try_csize,
+                      const int32_t *try_status, uint8_t *keep, uint32_t *full_idx, uint64_t *full_off,
+                      uint32_t *full_len, uint64_t *full_dst_off, uint32_t *totals2, void *workspace,
+                      size_t workspace_bytes, void *stream) {
+    if (!totals2) return fail(QLZX_R_BAD_ARG, "qlzx_write_decide: null totals2");
+    if (n) {
+        if (!val_off || !val_len || !totals || !try_idx || !try_len || !try_csize || !try_status || !keep ||
+            !full_idx || !full_off || !full_len || !full_dst_off)
+            return fail(QLZX_R_BAD_ARG, "qlzx_write_decide: null arg");
+        if (!workspace || workspace_bytes < qlzx_write_plan_workspace_size(n))
+            return fail(QLZX_R_WORKSPACE, "qlzx_write_decide: workspace too small");
+    }
+    const int e = qlzx::launch_write_decide(val_off, val_len, n, totals, try_idx, try_len, try_csize, try_status, keep,
+                                            full_idx, full_off, full_len, full_dst_off, totals2, workspace,
+                                            (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_write_decide", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+int qlzx_write_finish(const uint8_t *values, const uint64_t *val_off, const uint32_t *val_len, const uint8_t *keys,
+                      const uint64_t *key_off, const uint32_t *key_len, const uint32_t *flag, const int32_t *ver,
+                      const uint32_t *ts, uint32_t n, const uint32_t *totals, const uint32_t *try_idx,
+                      const uint32_t *try_len, const uint64_t *try_dst_off, const uint32_t *try_csize,
+                      const uint32_t *try_crc, const uint8_t *keep, const uint8_t *trial_buf,
+                      const uint32_t *totals2, const uint32_t *full_idx, const uint64_t *full_dst_off,
+                      const uint32_t *full_csize, const int32_t *full_status, const uint32_t *full_crc,
+                      const uint8_t *full_buf, uint8_t *out, uint64_t out_cap, int32_t *wr_status,
+                      uint64_t *rec_off, uint32_t *flag_out, uint32_t *vsz, uint32_t *crc, uint16_t *vhash,
+                      uint32_t *totals3, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!totals3) return fail(QLZX_R_BAD_ARG, "qlzx_write_finish: null totals3");
+    if (n) {
+        // trial_buf and full_buf may be null: nothing of them is read when their list is empty
+        if (!values || !val_off || !val_len || !keys || !key_off || !key_len || !flag || !ver || !ts || !totals ||
+            !try_idx || !try_len || !try_dst_off || !try_csize || !try_crc || !keep || !totals2 || !full_idx ||
+            !full_dst_off || !full_csize || !full_status || !full_crc || !out || !wr_status || !rec_off ||
+            !flag_out || !vsz || !crc)
+            return fail(QLZX_R_BAD_ARG, "qlzx_write_finish: null arg");
+        if ((uintptr_t)out & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_write_finish: out is not 16-B aligned");
+        if (!workspace || workspace_bytes < qlzx_write_plan_workspace_size(n))
+            return fail(QLZX_R_WORKSPACE, "qlzx_write_finish: workspace too small");
+    }
+    const qlzx::WrFinishArgs a{values,  keys,       trial_buf, full_buf, val_off,   key_off,  try_dst_off, full_dst_off,
+                               val_len, key_len,    flag,      ts,       totals,    try_idx,  try_len,     try_csize,
+                               try_crc, totals2,    full_idx,  full_csize, full_crc, ver,     full_status, keep};
+    const int e = qlzx::launch_write_finish(a, n, out, out_cap, wr_status, rec_off, flag_out, vsz, crc, vhash, totals3,
+                                            workspace, (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_write_finish", (hipError_t)e);
     return QLZX_R_OK;
 }
 

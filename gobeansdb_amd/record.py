@@ -15,6 +15,10 @@ The compress runs in qlzx_compress_batch with the value CRC fused (raw state 0),
 and the header+key prefix is folded in with qlzx_crc32_combine, because the
 header carries the compressed size.  Records come out 256-B padded and laid
 out back to back, ready to append.
+
+encode() drives the policy on the host in numpy; encode_batch() is the same step through the C
+ABI's qlzx_write_plan / qlzx_write_decide / qlzx_write_finish, with the policy, the sizes, the
+offsets and the CRCs kept on the device.
 """
 from __future__ import annotations
 
@@ -226,6 +230,126 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
     # crc field (records are 256-B aligned, so int32 words)
     out.view(torch.int32)[torch.from_numpy((roff // 4).astype(np.int64)).to(dev)] = crc_d
     return Encoded(out[:total], roff, flags, vsz.astype(np.uint32), crc)
+
+
+def not_compress_mask(not_compress) -> int:
+    """The QLZX_NC_* mask of a NotCompress set: one bit per row of _AV_SIGS whose answer is
+    listed, and NC_OTHER when None ("some other answer") is."""
+    mask = 0
+    for k, (_, _, name) in enumerate(_AV_SIGS):
+        if name in not_compress:
+            mask |= 1 << k
+    if None in not_compress:
+        mask |= _lib.NC_OTHER
+    return mask
+
+
+@dataclass
+class EncodedBatch:
+    """encode_batch's result; every tensor lives on the device."""
+    data: torch.Tensor        # uint8: the records back to back from offset 0 (capacity: the plan's bound)
+    offset: torch.Tensor      # int64 record offsets (0 for a record not written)
+    flag: torch.Tensor        # int32 flags as written (FLAG_COMPRESS added where kept)
+    vsz: torch.Tensor         # int32 stored value sizes
+    crc: torch.Tensor         # int32 record CRCs
+    status: torch.Tensor      # int32 enum qlzx_write_status
+    vhash: torch.Tensor       # int32 Getvhash of the original value
+    totals: torch.Tensor      # int32 [3]: records written, bytes written (lo, hi)
+    tried: torch.Tensor       # int32 record indices of the trial list (TryCompress's candidates), in order
+    counts: tuple[int, int, int, int] = (0, 0, 0, 0)   # OK records, ntry, nkeep, nfull (the two read-backs)
+
+
+def _dev_i32(a, n, dev, dtype=np.uint32):
+    if a is None:
+        return torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype)).view(np.int32)).to(dev)
+
+
+def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, vers=None, ts=None,
+                 not_compress=NOT_COMPRESS, max_key: int = 250, body_max: int = 50 << 20,
+                 workspace: batch.Workspace | None = None, stream=None, out: torch.Tensor | None = None,
+                 out_cap: int | None = None) -> EncodedBatch:
+    """TryCompress + encodeHeader + padding for n records whose keys and values live on the device
+    (qlzx_write_plan, qlzx_write_decide, qlzx_write_finish around two qlzx_compress_batch calls).
+    Sizes, flags, offsets and CRCs stay on the device; the host reads back the plan's and the
+    decision's totals only, to size the compress launches and the buffers.  `out` / `out_cap`
+    (optional) give the destination and the bytes of it that may be written."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return encode_batch(keys, values, flags, vers, ts, not_compress, max_key, body_max, workspace,
+                                None, out, out_cap)
+    L = _lib.lib()
+    dev = values.data.device
+    n = values.n
+    if keys.n != n:
+        raise ValueError("keys: one per value")
+    ws = workspace or batch.Workspace(dev)
+    st_ = batch._stream()
+    cap = max(n, 1)
+    flags, vers, ts = _dev_i32(flags, n, dev), _dev_i32(vers, n, dev, np.int32), _dev_i32(ts, n, dev)
+    i32 = lambda k=cap: torch.empty(k, dtype=torch.int32, device=dev)   # noqa: E731
+    i64 = lambda k=cap: torch.empty(k, dtype=torch.int64, device=dev)   # noqa: E731
+    status, try_idx, try_off, try_len, try_dst = i32(), i32(), i64(), i32(), i64()
+    totals = torch.zeros(7, dtype=torch.int32, device=dev)
+    ws_bytes = L.qlzx_write_plan_workspace_size(n)
+    wsp = lambda: ws.get(ws_bytes).data_ptr()   # noqa: E731  (the compress calls may grow the workspace)
+    _lib.check(L.qlzx_write_plan(values.data.data_ptr(), values.off.data_ptr(), values.length.data_ptr(),
+                                 keys.length.data_ptr(), flags.data_ptr(), vers.data_ptr(), n, max_key, body_max,
+                                 not_compress_mask(not_compress), status.data_ptr(), try_idx.data_ptr(),
+                                 try_off.data_ptr(), try_len.data_ptr(), try_dst.data_ptr(), totals.data_ptr(),
+                                 wsp(), ws_bytes, st_), "qlzx_write_plan")
+    t = totals.cpu().numpy().view(np.uint32)          # read-back 1: sizes the trial compress
+    nok, ntry, max_try = int(t[0]), int(t[1]), int(t[2])
+    trial_bytes, bound = int(t[3]) | (int(t[4]) << 32), int(t[5]) | (int(t[6]) << 32)
+    tbuf = tcs = tst = tcrc = None
+    if ntry:
+        tbuf = torch.empty(trial_bytes, dtype=torch.uint8, device=dev)
+        trial = batch.BlockBatch(values.data, try_off[:ntry], try_len[:ntry])
+        _, tcs, tst, tcrc = batch.compress(trial, batch.BlockBatch(tbuf, try_dst[:ntry], try_len[:ntry]),
+                                           crc_state=torch.zeros(ntry, dtype=torch.int32, device=dev),
+                                           max_len=max_try, workspace=ws)
+    else:
+        tcs, tst, tcrc = i32(1), i32(1), i32(1)
+    keep = torch.empty(cap, dtype=torch.uint8, device=dev)
+    full_idx, full_off, full_len, full_dst = i32(), i64(), i32(), i64()
+    totals2 = torch.zeros(5, dtype=torch.int32, device=dev)
+    _lib.check(L.qlzx_write_decide(values.off.data_ptr(), values.length.data_ptr(), n, totals.data_ptr(),
+                                   try_idx.data_ptr(), try_len.data_ptr(), tcs.data_ptr(), tst.data_ptr(),
+                                   keep.data_ptr(), full_idx.data_ptr(), full_off.data_ptr(), full_len.data_ptr(),
+                                   full_dst.data_ptr(), totals2.data_ptr(), wsp(), ws_bytes, st_),
+               "qlzx_write_decide")
+    t2 = totals2.cpu().numpy().view(np.uint32)        # read-back 2: sizes the full compress
+    nkeep, nfull, max_full = int(t2[0]), int(t2[1]), int(t2[2])
+    full_bytes = int(t2[3]) | (int(t2[4]) << 32)
+    fbuf = None
+    if nfull:
+        fbuf = torch.empty(full_bytes, dtype=torch.uint8, device=dev)
+        fsrc = batch.BlockBatch(values.data, full_off[:nfull], full_len[:nfull])
+        _, fcs, fst, fcrc = batch.compress(fsrc, batch.BlockBatch(fbuf, full_dst[:nfull], full_len[:nfull]),
+                                           crc_state=torch.zeros(nfull, dtype=torch.int32, device=dev),
+                                           max_len=max_full, workspace=ws)
+    else:
+        fcs, fst, fcrc = i32(1), i32(1), i32(1)
+    if out is None:
+        out = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
+    if out_cap is None:
+        out_cap = int(out.numel())
+    rec_off, flag_out, vsz, crc = i64(), i32(), i32(), i32()
+    vh16 = torch.empty(cap, dtype=torch.int16, device=dev)
+    totals3 = torch.zeros(3, dtype=torch.int32, device=dev)
+    _lib.check(L.qlzx_write_finish(values.data.data_ptr(), values.off.data_ptr(), values.length.data_ptr(),
+                                   keys.data.data_ptr(), keys.off.data_ptr(), keys.length.data_ptr(),
+                                   flags.data_ptr(), vers.data_ptr(), ts.data_ptr(), n, totals.data_ptr(),
+                                   try_idx.data_ptr(), try_len.data_ptr(), try_dst.data_ptr(), tcs.data_ptr(),
+                                   tcrc.data_ptr(), keep.data_ptr(), batch._ptr(tbuf), totals2.data_ptr(),
+                                   full_idx.data_ptr(), full_dst.data_ptr(), fcs.data_ptr(), fst.data_ptr(),
+                                   fcrc.data_ptr(), batch._ptr(fbuf), out.data_ptr(), out_cap, status.data_ptr(),
+                                   rec_off.data_ptr(), flag_out.data_ptr(), vsz.data_ptr(), crc.data_ptr(),
+                                   vh16.data_ptr(), totals3.data_ptr(), wsp(), ws_bytes, st_), "qlzx_write_finish")
+    return EncodedBatch(out, rec_off[:n], flag_out[:n], vsz[:n], crc[:n], status[:n],
+                        vh16[:n].to(torch.int32) & 0xFFFF, totals3, try_idx[:ntry], (nok, ntry, nkeep, nfull))
 
 
 def _copy(src: torch.Tensor, src_off, length, dst: torch.Tensor, dst_off, stream=None):

@@ -300,6 +300,91 @@ int qlzx_read_finish(const uint8_t *data, const uint64_t *rec_off, uint32_t n, c
                      int32_t *flag, int32_t *value_len, uint8_t *in_out, uint64_t *val_off, uint16_t *vhash,
                      int32_t *dec_status, void *stream);
 
+/* ---- batched record writes (a multi-SET) ----
+ * The mirror image of the batched read: Record.TryCompress (store/item.go:120-161), then
+ * WriteRecord.encodeHeader / getCRC / append with the 256-B padding (store/datafile.go:66-88,
+ * 307-330) for n records whose keys and values are resident in device memory, as
+ * dataChunk.flush (store/datachunk.go:88-120) and AppendRecordGC (:56-79) run them once per
+ * record.  Record i: value values[val_off[i] ..+ val_len[i]), key keys[key_off[i] ..+ key_len[i]),
+ * flag[i], ver[i], ts[i].  Five calls, two small read-backs (totals, totals2):
+ *   qlzx_write_plan; qlzx_compress_batch over the trial list (crc_state = zeros; skipped when
+ *   ntry == 0); qlzx_write_decide; qlzx_compress_batch over the full list (crc_state = zeros;
+ *   skipped when nfull == 0); qlzx_write_finish.
+ * Device pointers only; nothing allocates; every launch goes on `stream`.  One workspace of
+ * qlzx_write_plan_workspace_size(n) bytes serves the three calls (no state is carried in it).
+ * enum qlzx_write_status: KEY_SIZE ksz == 0 || ksz > max_key, VALUE_SIZE vlen > body_max (the
+ * limits qlzx_read_plan enforces: whatever this writes, that reads), NO_SPACE: the record would
+ * end past out_cap (qlzx_write_finish; a memory-safety guard, nothing of it is written).
+ * not_compress: the NotCompress set (store/item.go:114-118) as one bit per row of
+ * http.DetectContentType's audio/video table (Go 1.13 net/http/sniff.go, table order) plus one
+ * for every other answer; a record whose value's first bytes give a listed answer is not tried. */
+enum qlzx_write_status { QLZX_WR_OK = 0, QLZX_WR_KEY_SIZE, QLZX_WR_VALUE_SIZE, QLZX_WR_NO_SPACE };
+#define QLZX_NC_AUDIO_BASIC 0x01u
+#define QLZX_NC_AUDIO_AIFF 0x02u
+#define QLZX_NC_AUDIO_MPEG 0x04u
+#define QLZX_NC_APPLICATION_OGG 0x08u
+#define QLZX_NC_AUDIO_MIDI 0x10u
+#define QLZX_NC_VIDEO_AVI 0x20u
+#define QLZX_NC_AUDIO_WAVE 0x40u
+#define QLZX_NC_OTHER 0x80u
+#define QLZX_NC_DEFAULT (QLZX_NC_AUDIO_MPEG | QLZX_NC_AUDIO_WAVE) /* store/config_default.go:46-49 */
+/* Workspace of the three qlzx_write_* calls for n records. */
+size_t qlzx_write_plan_workspace_size(uint32_t n);
+/* TryCompress's candidates and the trial list.
+ *   wr_status[i]: OK, KEY_SIZE or VALUE_SIZE (24 + max_key + body_max + 9 + 256 must stay below
+ *   4 GiB).  An OK record is a candidate iff ver >= 0, flag & (0x10 | 0x10000) == 0,
+ *   pad256(24 + ksz + vlen) > 256 and the sniff of its value is not in not_compress.
+ *   try_*: the candidates in record order (capacity n each): try_idx (record), try_off (in
+ *   `values`), try_len = min(vlen, 10240), try_dst_off (256-B-aligned destinations try_len + 400
+ *   apart in one packed trial buffer).
+ *   totals[7] = {OK records, ntry, max try_len, trial buffer bytes (lo, hi), output bound bytes
+ *   (lo, hi)}; the bound is the sum of pad256(24 + ksz + vlen + 9) over the OK records (a kept
+ *   value can be a stored QuickLZ block, 9 bytes longer than the plain one).
+ * n == 0 returns QLZX_R_OK; nothing is launched or written (totals included). */
+int qlzx_write_plan(const uint8_t *values, const uint64_t *val_off, const uint32_t *val_len, const uint32_t *key_len,
+                    const uint32_t *flag, const int32_t *ver, uint32_t n, uint32_t max_key, uint64_t body_max,
+                    uint32_t not_compress, int32_t *wr_status, uint32_t *try_idx, uint64_t *try_off,
+                    uint32_t *try_len, uint64_t *try_dst_off, uint32_t *totals, void *workspace,
+                    size_t workspace_bytes, void *stream);
+/* The ratio test and the full-recompress list, after qlzx_compress_batch over the trial list
+ * (try_csize, try_status = its outputs; totals = qlzx_write_plan's, on the device).
+ *   keep[k] (capacity n) = try_status[k] is QLZX_OK and float32(try_csize[k]) /
+ *   float32(try_len[k]) <= 0.7f, IEEE single division and compare (store/item.go:145); a failed
+ *   compress is "not compressed", as the reference's !ok branches.
+ *   full_*: the kept trials with vlen > try_len, in record order (capacity n each): full_idx
+ *   (record), full_off, full_len = vlen, full_dst_off (full_len + 400 apart).
+ *   totals2[5] = {nkeep, nfull, max full_len, full buffer bytes (lo, hi)}.
+ * n == 0 returns QLZX_R_OK; nothing is launched or written (totals2 included). */
+int qlzx_write_decide(const uint64_t *val_off, const uint32_t *val_len, uint32_t n, const uint32_t *totals,
+                      const uint32_t *try_idx, const uint32_t *try_len, const uint32_t *try_csize,
+                      const int32_t *try_status, uint8_t *keep, uint32_t *full_idx, uint64_t *full_off,
+                      uint32_t *full_len, uint64_t *full_dst_off, uint32_t *totals2, void *workspace,
+                      size_t workspace_bytes, void *stream);
+/* Sizes, flags, offsets, CRCs and the records themselves, after qlzx_compress_batch over the full
+ * list (full_csize, full_status, full_crc = its outputs; a full compress that failed leaves the
+ * value raw).  try_crc / full_crc: the compressor's crc_out for crc_state = 0.
+ *   Records lie back to back in `out` (16-B aligned) from offset 0 in record order: rec_off[i] =
+ *   the exclusive scan of pad256(24 + ksz + vsz) over the OK records; failed records take no
+ *   space.  Each is crc ‖ ts ‖ flag ‖ ver ‖ ksz ‖ vsz ‖ key ‖ value ‖ zeros to 256, the value
+ *   taken from `values`, trial_buf or full_buf (both nullable when their list is empty); the
+ *   padding is written here, `out` need not be zeroed.  A record that would end past out_cap gets
+ *   QLZX_WR_NO_SPACE in wr_status (in/out) and nothing of it is written.
+ *   flag_out (FLAG_COMPRESS added where kept), vsz, crc = ~crc_write(~0, header[4:24] ‖ key ‖
+ *   value); vhash (nullable) = Getvhash of the ORIGINAL value (CalcValueHash runs before
+ *   TryCompress, store/item.go:102).  Records not written get rec_off = flag_out = vsz = crc =
+ *   vhash = 0.  totals3[3] = {records written, bytes written (lo, hi)}.
+ * n == 0 returns QLZX_R_OK; nothing is launched or written (totals3 included). */
+int qlzx_write_finish(const uint8_t *values, const uint64_t *val_off, const uint32_t *val_len, const uint8_t *keys,
+                      const uint64_t *key_off, const uint32_t *key_len, const uint32_t *flag, const int32_t *ver,
+                      const uint32_t *ts, uint32_t n, const uint32_t *totals, const uint32_t *try_idx,
+                      const uint32_t *try_len, const uint64_t *try_dst_off, const uint32_t *try_csize,
+                      const uint32_t *try_crc, const uint8_t *keep, const uint8_t *trial_buf,
+                      const uint32_t *totals2, const uint32_t *full_idx, const uint64_t *full_dst_off,
+                      const uint32_t *full_csize, const int32_t *full_status, const uint32_t *full_crc,
+                      const uint8_t *full_buf, uint8_t *out, uint64_t out_cap, int32_t *wr_status,
+                      uint64_t *rec_off, uint32_t *flag_out, uint32_t *vsz, uint32_t *crc, uint16_t *vhash,
+                      uint32_t *totals3, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Getvhash (store/item.go:89-100, Fnv1a of utils/hash.go:8-16) of n values. */
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,
                      void *stream);
