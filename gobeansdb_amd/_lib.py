@@ -27,6 +27,10 @@ RD_NAMES = ["RD_OK", "RD_ALIGN", "RD_EOF_HEADER", "RD_KEY_SIZE", "RD_VALUE_SIZE"
 # enum qlzx_write_status (qlzx_write_plan / qlzx_write_finish's verdict per record)
 WR_OK, WR_KEY_SIZE, WR_VALUE_SIZE, WR_NO_SPACE = range(4)
 WR_NAMES = ["WR_OK", "WR_KEY_SIZE", "WR_VALUE_SIZE", "WR_NO_SPACE"]
+# enum qlzx_gc_status (qlzx_gc_plan / qlzx_gc_rewrite's verdict per record)
+GC_WRITTEN, GC_DROPPED, GC_BAD_RECORD, GC_NO_CHUNK, GC_NO_SPACE = range(5)
+GC_NAMES = ["GC_WRITTEN", "GC_DROPPED", "GC_BAD_RECORD", "GC_NO_CHUNK", "GC_NO_SPACE"]
+MAX_NUM_CHUNK = 998   # store/data.go:15: the most destination chunks qlzx_gc_plan takes
 # QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
 # order, and one for every other answer
 NC_AUDIO_BASIC, NC_AUDIO_AIFF, NC_AUDIO_MPEG, NC_APPLICATION_OGG, NC_AUDIO_MIDI, NC_VIDEO_AVI, NC_AUDIO_WAVE, \
@@ -134,6 +138,12 @@ def lib() -> ctypes.CDLL:
     L.qlzx_write_decide.restype = ctypes.c_int
     L.qlzx_write_finish.argtypes = [vp] * 9 + [u32] + [vp] * 16 + [u64] + [vp] * 8 + [sz, vp]
     L.qlzx_write_finish.restype = ctypes.c_int
+    L.qlzx_gc_workspace_size.argtypes = [u32, u32]
+    L.qlzx_gc_workspace_size.restype = sz
+    L.qlzx_gc_plan.argtypes = [vp, u64, vp, vp, u32, vp, u32, u64, u64, vp, u32] + [vp] * 7 + [sz, vp]
+    L.qlzx_gc_plan.restype = ctypes.c_int
+    L.qlzx_gc_rewrite.argtypes = [vp, u64, vp, vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp, sz, vp]
+    L.qlzx_gc_rewrite.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

@@ -28,6 +28,7 @@
 #include "qlzx_replay.hip"
 #include "qlzx_read.hip"
 #include "qlzx_write.hip"
+#include "qlzx_gc.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -428,6 +429,56 @@ int qlzx_write_finish(const uint8_t *values, const uint64_t *val_off, const uint
     const int e = qlzx::launch_write_finish(a, n, out, out_cap, wr_status, rec_off, flag_out, vsz, crc, vhash, totals3,
                                             workspace, (hipStream_t)stream);
     if (e) return fail(QLZX_R_HIP, "qlzx_write_finish", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+size_t qlzx_gc_workspace_size(uint32_t cap, uint32_t max_chunks) {
+    return qlzx::gc_ws_layout(cap, max_chunks, nullptr, nullptr);
+}
+
+int qlzx_gc_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                 const uint8_t *keep, uint32_t max_key, uint64_t body_max, uint64_t data_file_max,
+                 const uint64_t *chunk_head, uint32_t max_chunks, int32_t *gc_status, uint32_t *new_chunk,
+                 uint64_t *new_off, uint64_t *chunk_base, uint64_t *chunk_bytes, uint32_t *totals, void *workspace,
+                 size_t workspace_bytes, void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    if ((!data && size) || !rec_off || !result || !keep || !chunk_head || !gc_status || !new_chunk || !new_off ||
+        !chunk_base || !chunk_bytes || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: null arg");
+    if (max_chunks < 1 || max_chunks > 998) return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: max_chunks is 1 to 998");
+    if ((uintptr_t)data & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: data is not 16-B aligned");
+    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: file too large");
+    if (body_max > 0xffffffffull - 24 - 256 - max_key)
+        return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: 24 + max_key + body_max + 256 is 4 GiB or more");
+    if (!workspace || workspace_bytes < qlzx_gc_workspace_size(cap, max_chunks))
+        return fail(QLZX_R_WORKSPACE, "qlzx_gc_plan: workspace too small");
+    const int e = qlzx::launch_gc_plan(data, size, rec_off, result, cap, keep, max_key, body_max, data_file_max,
+                                       chunk_head, max_chunks, gc_status, new_chunk, new_off, chunk_base, chunk_bytes,
+                                       totals, workspace, (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_gc_plan", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+int qlzx_gc_rewrite(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                    const uint64_t *chunk_head, uint32_t max_chunks, const uint32_t *new_chunk,
+                    const uint64_t *new_off, const uint64_t *chunk_base, uint8_t *out, uint64_t out_cap,
+                    int32_t *gc_status, uint32_t *crc, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                    void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    if ((!data && size) || !rec_off || !result || !chunk_head || !new_chunk || !new_off || !chunk_base ||
+        (!out && out_cap) || !gc_status || !crc || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_gc_rewrite: null arg");
+    if (max_chunks < 1 || max_chunks > 998) return fail(QLZX_R_BAD_ARG, "qlzx_gc_rewrite: max_chunks is 1 to 998");
+    if (((uintptr_t)data | (uintptr_t)out) & 15u)
+        return fail(QLZX_R_BAD_ARG, "qlzx_gc_rewrite: data and out are not 16-B aligned");
+    // records are written in parallel: a chunk cannot be rewritten onto itself
+    if (size && out_cap && (uintptr_t)out < (uintptr_t)data + size && (uintptr_t)data < (uintptr_t)out + out_cap)
+        return fail(QLZX_R_BAD_ARG, "qlzx_gc_rewrite: out overlaps data");
+    if (!workspace || workspace_bytes < qlzx_gc_workspace_size(cap, max_chunks))
+        return fail(QLZX_R_WORKSPACE, "qlzx_gc_rewrite: workspace too small");
+    const qlzx::GcIn in{data, size, rec_off, chunk_head, new_off, chunk_base, new_chunk, max_chunks, out, out_cap};
+    const int e = qlzx::launch_gc_rewrite(in, result, cap, gc_status, crc, totals, workspace, (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_gc_rewrite", (hipError_t)e);
     return QLZX_R_OK;
 }
 

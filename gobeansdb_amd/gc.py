@@ -15,6 +15,10 @@ those rotations (host, one pass over the sizes); the copies (qlzx_copy_batch) an
 CRCs (qlzx_crc32_batch over the copied records) run in libqlzx.so.  The rewritten
 CRC must equal the stored one (the reader verified it); `crc_mismatch` counts the
 records where it does not, which would mean a corrupted copy.
+
+rewrite_batch is the same rewrite with every per-record step on the device (SURVEY §8 f4b,
+qlzx_gc_plan / qlzx_gc_rewrite, csrc/qlzx_gc.hip): the planning included, each record read once
+and written once with its CRC computed on the way, and only totals[8] and the chunk sizes read back.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ import torch
 
 from . import _lib, batch
 from .record import _copy, _dev_u32, _dev_u64
-from .replay import HDR
+from .replay import BODY_MAX, HDR, MAX_KEY_LEN
 
 DATA_FILE_MAX = 4000 << 20   # store/config_default.go:39
 
@@ -71,6 +75,85 @@ def plan(recsize: np.ndarray, dst_head: int = 0, data_file_max: int = DATA_FILE_
         head = int(cs[fit - 1])
         i += fit
     return chunk, off
+
+
+@dataclass
+class GCBatch:
+    """rewrite_batch's result; the per-record tensors live on the device, one entry per record of
+    rec_off (kept or not)."""
+    status: torch.Tensor         # int32 enum qlzx_gc_status
+    new_chunk: torch.Tensor      # int32 destination chunk index (0 for a record not placed)
+    new_off: torch.Tensor        # int64 offset in that chunk, from the chunk's start (0 if not placed)
+    crc: torch.Tensor            # int32 recomputed record CRCs (0 for a record not written)
+    chunks: list[torch.Tensor]   # views into `out`: destination chunk c's bytes from its head on
+    out: torch.Tensor            # uint8 destination buffer, the chunks packed back to back
+    totals: np.ndarray           # uint32 [8], as qlzx_gc_plan / qlzx_gc_rewrite leave them
+    chunk_bytes: np.ndarray      # uint64 [chunks used]
+
+    def result(self) -> GCResult:
+        """The fields gc.rewrite returns, over the records written (this reads the tensors back)."""
+        w = (self.status == _lib.GC_WRITTEN).cpu().numpy()
+        chunks = self.chunks or [self.out[:0]]
+        return GCResult(chunks, self.new_chunk.cpu().numpy()[w].astype(np.int32),
+                        self.new_off.cpu().numpy().view(np.uint64)[w],
+                        self.crc.cpu().numpy().view(np.uint32)[w], int(self.totals[6]))
+
+
+def rewrite_batch(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_head: int = 0,
+                  data_file_max: int = DATA_FILE_MAX, next_heads=(), max_chunks: int | None = None,
+                  out: torch.Tensor | None = None, stream=None) -> GCBatch:
+    """gc.rewrite with every per-record step on the device (qlzx_gc_plan, qlzx_gc_rewrite): sizes,
+    destinations, statuses and CRCs stay there, the records are read once and written once with the
+    CRC computed on the way.  The host reads back totals[8] and the chunk sizes, nothing else.
+    Destination chunk c starts at chunk_head(c, dst_head, next_heads); at most max_chunks
+    (default: as many as the library takes) are used, later survivors get GC_NO_CHUNK.  `out`
+    (optional, 16-B aligned, not overlapping data) receives the chunks packed back to back;
+    pad256(len(data)) bytes always suffice for record offsets that came from replay.index."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return rewrite_batch(data, rec_off, keep, dst_head, data_file_max, next_heads, max_chunks, out, None)
+    L = _lib.lib()
+    dev = data.device
+    size, n = int(data.numel()), int(rec_off.numel())
+    if keep.numel() != n:
+        raise ValueError("keep: one per record")
+    if max_chunks is None:
+        max_chunks = _lib.MAX_NUM_CHUNK
+    st_ = batch._stream()
+    cap = max(n, 1)
+    heads = np.zeros(max_chunks, np.uint64)                # chunk_head(c) for every c: 0 past next_heads
+    known = [int(dst_head), *map(int, next_heads)][:max_chunks]
+    heads[:len(known)] = known
+    heads = _dev_u64(heads, dev)
+    result = torch.tensor([n, 0, 0, 0], dtype=torch.int32, device=dev)
+    keep8 = keep.to(device=dev, dtype=torch.uint8).contiguous()
+    rec_off = rec_off.to(device=dev, dtype=torch.int64).contiguous()
+    status = torch.empty(cap, dtype=torch.int32, device=dev)
+    new_chunk, crc = torch.empty_like(status), torch.empty_like(status)
+    new_off = torch.empty(cap, dtype=torch.int64, device=dev)
+    chunk_base = torch.zeros(max_chunks, dtype=torch.int64, device=dev)
+    chunk_bytes = torch.zeros(max_chunks, dtype=torch.int64, device=dev)
+    totals = torch.zeros(8, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty(max((size + 255) // 256 * 256, 16), dtype=torch.uint8, device=dev)
+    ws_bytes = L.qlzx_gc_workspace_size(cap, max_chunks)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if n:
+        _lib.check(L.qlzx_gc_plan(batch._ptr(data) if size else None, size, rec_off.data_ptr(), result.data_ptr(),
+                                  cap, keep8.data_ptr(), MAX_KEY_LEN, BODY_MAX, data_file_max, heads.data_ptr(),
+                                  max_chunks, status.data_ptr(), new_chunk.data_ptr(), new_off.data_ptr(),
+                                  chunk_base.data_ptr(), chunk_bytes.data_ptr(), totals.data_ptr(), ws.data_ptr(),
+                                  ws_bytes, st_), "qlzx_gc_plan")
+        _lib.check(L.qlzx_gc_rewrite(batch._ptr(data) if size else None, size, rec_off.data_ptr(),
+                                     result.data_ptr(), cap, heads.data_ptr(), max_chunks, new_chunk.data_ptr(),
+                                     new_off.data_ptr(), chunk_base.data_ptr(), out.data_ptr(), int(out.numel()),
+                                     status.data_ptr(), crc.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes,
+                                     st_), "qlzx_gc_rewrite")
+    t = totals.cpu().numpy().view(np.uint32)               # the read-backs: totals and the chunk sizes
+    cb = chunk_bytes[:max(int(t[3]), 1)].cpu().numpy().view(np.uint64)[:int(t[3])]
+    base = np.concatenate([[0], np.cumsum(cb.astype(np.int64))])
+    chunks = [out[int(base[c]):int(base[c + 1])] for c in range(len(cb))]
+    return GCBatch(status[:n], new_chunk[:n], new_off[:n], crc[:n], chunks, out, t, cb)
 
 
 def rewrite(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_head: int = 0,

@@ -385,6 +385,70 @@ int qlzx_write_finish(const uint8_t *values, const uint64_t *val_off, const uint
                       uint64_t *rec_off, uint32_t *flag_out, uint32_t *vsz, uint32_t *crc, uint16_t *vhash,
                       uint32_t *totals3, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- GC rewrite of a chunk ----
+ * The record loop of GCMgr.gc (store/gc.go:268-353) over one source chunk resident in device
+ * memory: every record the stream reader returned that the caller calls live is appended to the
+ * destination in order, as dataChunk.AppendRecordGC -> WriteRecord.append does
+ * (store/datachunk.go:56-79, store/datafile.go:307-330): the header re-encoded with its CRC
+ * recomputed (store/datafile.go:66-88), zero padding to 256 B, and the next destination chunk
+ * whenever recsize + writingHead > DataFileMax (store/gc.go:320-336; the reference moves once and
+ * then appends whatever the size, so a record larger than data_file_max gets a chunk to itself).
+ * rec_off / result / cap are qlzx_replay_index's outputs, used as qlzx_replay_plan uses them
+ * (result[0] = the record count, read on the device; cap = the capacity of every per-record
+ * array), so index -> qlzx_gc_plan -> qlzx_gc_rewrite needs no read-back and no synchronisation in
+ * between.  rec_off is in append order; entries need not be increasing or distinct.  keep[j] != 0:
+ * record j is live (the HTree / hint / collision lookups behind isNewest are the caller's).
+ * chunk_head[c], c < max_chunks (1..998, MAX_NUM_CHUNK of store/data.go:15): the writingHead at
+ * which destination chunk c starts (beginGCWriting, store/datachunk.go:185-199), taken as given.
+ * Device pointers only; nothing allocates; every launch goes on `stream`.  One workspace of
+ * qlzx_gc_workspace_size(cap, max_chunks) bytes serves both calls (no state is carried in it).
+ * enum qlzx_gc_status: DROPPED keep[j] == 0; BAD_RECORD a kept record that fails readRecordAt's
+ * size checks (rec_off % 256, header inside size, 1 <= ksz <= max_key, vsz <= body_max, body
+ * inside size: store/datafile.go:123-149; the CRC is not a check here, see qlzx_gc_rewrite), it
+ * takes no space and nothing past the failing check is read; NO_CHUNK the rotation would need
+ * chunk max_chunks: that record and every later survivor; NO_SPACE the record would end past
+ * out_cap (qlzx_gc_rewrite; a memory-safety guard, nothing of it is written). */
+enum qlzx_gc_status { QLZX_GC_WRITTEN = 0, QLZX_GC_DROPPED, QLZX_GC_BAD_RECORD, QLZX_GC_NO_CHUNK, QLZX_GC_NO_SPACE };
+/* Workspace of the two qlzx_gc_* calls. */
+size_t qlzx_gc_workspace_size(uint32_t cap, uint32_t max_chunks);
+/* Where every kept record goes.  data is 16-B aligned; size / 256 < 0xfffffff0; 24 + max_key +
+ * body_max + 256 must stay below 4 GiB.
+ *   gc_status[j]: WRITTEN (placed), DROPPED, BAD_RECORD or NO_CHUNK.
+ *   new_chunk[j] / new_off[j]: the destination chunk of record j and its offset in that chunk
+ *   measured from the chunk's start (the reference's newPos); 0 / 0 for a record not placed.
+ *   chunk_bytes[c] / chunk_base[c] (max_chunks entries each): the bytes written into chunk c and
+ *   their exclusive scan: chunk c's bytes, from its head on, lie packed at out + chunk_base[c].
+ *   totals[8] = {records, keep requested, placed, chunks used (last index + 1; 0 if none placed),
+ *   bytes (lo, hi), CRC mismatches (0 here), BAD_RECORD + NO_CHUNK + NO_SPACE}.
+ *   The bytes never exceed pad256(size) when rec_off comes from qlzx_replay_index (its records
+ *   are disjoint), so a caller may allocate that much for `out` and skip the read-back.
+ * Entries j >= result[0] of the per-record arrays are not written.  cap == 0 returns QLZX_R_OK;
+ * nothing is launched or written.  result[0] == 0 on the device gives zero totals. */
+int qlzx_gc_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                 const uint8_t *keep, uint32_t max_key, uint64_t body_max, uint64_t data_file_max,
+                 const uint64_t *chunk_head, uint32_t max_chunks, int32_t *gc_status, uint32_t *new_chunk,
+                 uint64_t *new_off, uint64_t *chunk_base, uint64_t *chunk_bytes, uint32_t *totals, void *workspace,
+                 size_t workspace_bytes, void *stream);
+/* The records themselves, after qlzx_gc_plan (gc_status, new_chunk, new_off, chunk_base, totals =
+ * its outputs, on the device).  Each WRITTEN record's 24 + ksz + vsz bytes are read once, its CRC
+ * ~crc_write(~0, header[4:24] ‖ key ‖ value) is computed in the same pass, and bytes, zero
+ * padding to 256 and the CRC word are written at out + chunk_base[c] + new_off - chunk_head[c];
+ * `out` need not be zeroed.  data and out are 16-B aligned, and [out, out + out_cap) must not
+ * overlap [data, data + size): the reference can rewrite a chunk onto itself, records written in
+ * parallel cannot.
+ *   crc[j]: the recomputed CRC, 0 for a record not written.  A recomputed CRC that differs from
+ *   the stored word does not stop the write (WriteRecord.append always re-encodes); totals[6]
+ *   counts those records.
+ *   A record that would end past out_cap gets QLZX_GC_NO_SPACE in gc_status (in/out) and nothing
+ *   of it is written; totals (in/out) [2], [4], [5] and [7] are adjusted.  new_chunk, new_off and
+ *   the chunk arrays are inputs and keep the plan's values.
+ * cap == 0 returns QLZX_R_OK; nothing is launched or written. */
+int qlzx_gc_rewrite(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                    const uint64_t *chunk_head, uint32_t max_chunks, const uint32_t *new_chunk,
+                    const uint64_t *new_off, const uint64_t *chunk_base, uint8_t *out, uint64_t out_cap,
+                    int32_t *gc_status /* in/out */, uint32_t *crc, uint32_t *totals /* in/out */, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 /* Getvhash (store/item.go:89-100, Fnv1a of utils/hash.go:8-16) of n values. */
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,
                      void *stream);
