@@ -30,6 +30,12 @@ WR_NAMES = ["WR_OK", "WR_KEY_SIZE", "WR_VALUE_SIZE", "WR_NO_SPACE"]
 # enum qlzx_gc_status (qlzx_gc_plan / qlzx_gc_rewrite's verdict per record)
 GC_WRITTEN, GC_DROPPED, GC_BAD_RECORD, GC_NO_CHUNK, GC_NO_SPACE = range(5)
 GC_NAMES = ["GC_WRITTEN", "GC_DROPPED", "GC_BAD_RECORD", "GC_NO_CHUNK", "GC_NO_SPACE"]
+# qlzx_hint_plan / qlzx_hint_write: the entries of totals[10], and totals[8]'s QLZX_HINT_NO_SPACE
+HINT_CONSUMED, HINT_NUM_KEY, HINT_N_INDEX, HINT_DATASIZE, HINT_INDEX_OFF_LO, HINT_INDEX_OFF_HI, HINT_BYTES_LO, \
+    HINT_BYTES_HI, HINT_STATUS, HINT_SKIPPED = range(10)
+HINT_NO_SPACE = 1
+HINT_SPLIT_CAP = 1 << 20        # store/config_default.go:28 (SplitCapStr "1M")
+HINT_INDEX_INTERVAL = 4 << 10   # store/config_default.go:29 (IndexIntervalSizeStr "4K")
 MAX_NUM_CHUNK = 998   # store/data.go:15: the most destination chunks qlzx_gc_plan takes
 # QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
 # order, and one for every other answer
@@ -144,6 +150,14 @@ def lib() -> ctypes.CDLL:
     L.qlzx_gc_plan.restype = ctypes.c_int
     L.qlzx_gc_rewrite.argtypes = [vp, u64, vp, vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp, sz, vp]
     L.qlzx_gc_rewrite.restype = ctypes.c_int
+    L.qlzx_keyhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
+    L.qlzx_keyhash_batch.restype = ctypes.c_int
+    L.qlzx_hint_workspace_size.argtypes = [u32]
+    L.qlzx_hint_workspace_size.restype = sz
+    L.qlzx_hint_plan.argtypes = [vp, u64, vp, vp, u32, vp, vp, u32, u32, ctypes.c_int64, u32] + [vp] * 6 + [sz, vp]
+    L.qlzx_hint_plan.restype = ctypes.c_int
+    L.qlzx_hint_write.argtypes = [vp, u64, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.qlzx_hint_write.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

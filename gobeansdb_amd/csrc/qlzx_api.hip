@@ -29,6 +29,7 @@
 #include "qlzx_read.hip"
 #include "qlzx_write.hip"
 #include "qlzx_gc.hip"
+#include "qlzx_hint.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -479,6 +480,61 @@ int qlzx_gc_rewrite(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
     const qlzx::GcIn in{data, size, rec_off, chunk_head, new_off, chunk_base, new_chunk, max_chunks, out, out_cap};
     const int e = qlzx::launch_gc_rewrite(in, result, cap, gc_status, crc, totals, workspace, (hipStream_t)stream);
     if (e) return fail(QLZX_R_HIP, "qlzx_gc_rewrite", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+int qlzx_keyhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint64_t *out,
+                       void *stream) {
+    if (n == 0) return QLZX_R_OK;
+    if (!src || !off || !len || !out) return fail(QLZX_R_BAD_ARG, "qlzx_keyhash_batch: null arg");
+    hipLaunchKernelGGL(qlzx::k_keyhash, dim3(qlzx::hint_grid(n)), dim3(256), 0, (hipStream_t)stream, src, off, len, n,
+                       out);
+    HIP_OK(hipGetLastError());
+    return QLZX_R_OK;
+}
+
+size_t qlzx_hint_workspace_size(uint32_t cap) { return qlzx::hint_ws_layout(cap, nullptr, nullptr); }
+
+int qlzx_hint_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                   const int32_t *hdr, const uint64_t *keyhash, uint32_t first, uint32_t split_cap,
+                   int64_t index_interval, uint32_t max_offset_in, uint32_t *item_rec, uint64_t *item_hash,
+                   uint64_t *item_off, uint32_t *index_item, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                   void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    // keyhash may be null: the default hash of the record's key
+    if ((!data && size) || !rec_off || !result || !hdr || !item_rec || !item_hash || !item_off || !index_item ||
+        !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_hint_plan: null arg");
+    if (split_cap == 0) return fail(QLZX_R_BAD_ARG, "qlzx_hint_plan: split_cap is 1 or more");
+    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_hint_plan: file too large");
+    if (!workspace || workspace_bytes < qlzx_hint_workspace_size(cap))
+        return fail(QLZX_R_WORKSPACE, "qlzx_hint_plan: workspace too small");
+    const qlzx::HintIn in{data, size, rec_off, hdr, cap};
+    const int e = qlzx::launch_hint_plan(in, result, keyhash, first, split_cap, index_interval, max_offset_in,
+                                         item_rec, item_hash, item_off, index_item, totals, workspace,
+                                         (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_hint_plan", (hipError_t)e);
+    return QLZX_R_OK;
+}
+
+int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off, uint32_t cap, const int32_t *hdr,
+                    const uint16_t *vhash, uint32_t chunk_id, const uint32_t *item_rec, const uint64_t *item_hash,
+                    const uint64_t *item_off, const uint32_t *index_item, uint8_t *out, uint64_t out_cap,
+                    uint32_t *totals, void *workspace, size_t workspace_bytes, void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    if ((!data && size) || !rec_off || !hdr || !vhash || !item_rec || !item_hash || !item_off || !index_item ||
+        (!out && out_cap) || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_hint_write: null arg");
+    if ((uintptr_t)out & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_hint_write: out is not 16-B aligned");
+    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_hint_write: file too large");
+    if (!workspace || workspace_bytes < qlzx_hint_workspace_size(cap))
+        return fail(QLZX_R_WORKSPACE, "qlzx_hint_write: workspace too small");
+    qlzx::HintFile f{};
+    f.in = qlzx::HintIn{data, size, rec_off, hdr, cap};
+    f.vhash = vhash, f.item_rec = item_rec, f.index_item = index_item, f.item_hash = item_hash, f.item_off = item_off;
+    f.chunk_id = chunk_id;
+    const int e = qlzx::launch_hint_write(f, out, out_cap, totals, (hipStream_t)stream);
+    if (e) return fail(QLZX_R_HIP, "qlzx_hint_write", (hipError_t)e);
     return QLZX_R_OK;
 }
 

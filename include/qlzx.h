@@ -449,6 +449,76 @@ int qlzx_gc_rewrite(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
                     int32_t *gc_status /* in/out */, uint32_t *crc, uint32_t *totals /* in/out */, void *workspace,
                     size_t workspace_bytes, void *stream);
 
+/* ---- Hint split file of a replayed chunk ----
+ * getKeyHashDefalut (store/key.go:41-59) of n keys: out[i] = (uint64)fnv1a(key_i) << 32 |
+ * murmur3_32(key_i, seed 0), fnv1a the sign-extending variant of store/key.go:47-55
+ * (h ^= uint32(int8(b))), murmur3_32 MurmurHash3_x86_32 (little-endian 4-byte blocks, a 0..3 byte
+ * tail, fmix32).  len[i] is 0..255; key i is the bytes src + off[i] .. + len[i], at any alignment.
+ * n == 0 returns QLZX_R_OK. */
+int qlzx_keyhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint64_t *out,
+                       void *stream);
+/* The split file buildHintFromData (store/bucket.go:89-117) emits for a chunk, from the records
+ * of a replay that are resident in device memory: HintBuffer.Set over the records in append order
+ * (store/hint.go:121-161), HintBuffer.Dump's sort by (keyhash, key) (:181-208, byKeyHash.Less
+ * :334-352), and hintFileWriter's head, items and index (store/hintfile.go:142-212,
+ * store/hintindex.go:140-150).  One qlzx_hint_plan / qlzx_hint_write pair builds ONE split file;
+ * a chunk with more than split_cap distinct keys takes one pair per split (hintChunk.setItem ->
+ * rotate, store/hint.go:241-252): first += totals[0], max_offset_in = totals[3].
+ * data / size / rec_off / result / cap as qlzx_gc_plan takes them (result[0] = the record count,
+ * read on the device; n = min(result[0], cap)); hdr is qlzx_replay_plan's (6 ints per record: ver
+ * = hdr[6j+3], ksz = hdr[6j+4], vsz = hdr[6j+5]), vhash qlzx_replay_finish's.  keyhash: NULL for
+ * the default hash above of the key at data + rec_off[j] + 24, or one u64 per record (the
+ * reference's replaceable getKeyHash).  Device pointers only; nothing allocates; every launch goes
+ * on `stream`; no host synchronisation.  One workspace of qlzx_hint_workspace_size(cap) bytes
+ * serves both calls (no state is carried in it; the radix sort's temporary storage lives there).
+ * Over the records first .. n-1:
+ *   - two records are one item iff keyhash and key bytes are equal; the item is the last of them
+ *     below the cut (a later Set overwrites the slot);
+ *   - the cut c is the first record that would be distinct item split_cap + 1 (Set returns false,
+ *     store/hint.go:140-147); repeats of a taken key after the buffer is full are still taken.
+ *     consumed = c - first, or n - first without a cut;
+ *   - datasize = max(max_offset_in, uint32(rec_off[j]) + pad256(24 + ksz + vsz) over every taken
+ *     record j < c, and uint32(rec_off[c]) when there is a cut);
+ *   - items ascend by keyhash, then by key bytes, the shorter prefix first;
+ *   - file: 16-B head {indexOffset i64, numKey u32, datasize u32}; per item 23 bytes {keyhash u64,
+ *     chunk_id u32, offset u32, ver i32, vhash u16, ksz u8} and the key; item k at o_k = 16 + the
+ *     exclusive scan of 23 + ksz; indexOffset = o_numKey; then 16 bytes {keyhash u64, offset i64}
+ *     per index entry: walking the items with last = 0, item k is an entry when o_k - last >
+ *     index_interval - 23 - 256 (signed 64-bit), and then last = o_k (store/hintfile.go:174-176);
+ *   - a record with ksz == 0, ksz > 255 or rec_off + 24 + ksz > size is skipped: no item, no part
+ *     in the cut or in datasize, nothing past the failing check is read (records from
+ *     qlzx_replay_index never are).  totals[9] counts the skipped records among the consumed.
+ * A run of equal keyhash is normally versions of one key and costs one key comparison per record;
+ * a run with different keys (a 64-bit collision or a caller's keyhash) is ranked by one wave with
+ * L^2 key comparisons for a run of L records: correct, not fast. */
+#define QLZX_HINT_NO_SPACE 1
+/* Workspace of the two qlzx_hint_* calls. */
+size_t qlzx_hint_workspace_size(uint32_t cap);
+/* The items, their order and file offsets, and the index entries.  size / 256 < 0xfffffff0;
+ * split_cap >= 1 (Conf.SplitCap); index_interval = Conf.IndexIntervalSize.
+ *   item_rec[k] / item_hash[k] / item_off[k]: record index, keyhash and file offset of sorted item
+ *   k; index_item[m]: the item of index entry m (capacity cap each).
+ *   totals[10] = {consumed, numKey, index entries, datasize, indexOffset (lo, hi), file bytes
+ *   (lo, hi), 0, skipped}.  numKey == 0 (first >= n, or every record skipped): file bytes = 0, the
+ *   reference never dumps an empty buffer (needDump, store/hint.go:210-212).
+ * cap == 0 returns QLZX_R_OK; nothing is launched or written. */
+int qlzx_hint_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                   const int32_t *hdr, const uint64_t *keyhash, uint32_t first, uint32_t split_cap,
+                   int64_t index_interval, uint32_t max_offset_in, uint32_t *item_rec, uint64_t *item_hash,
+                   uint64_t *item_off, uint32_t *index_item, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                   void *stream);
+/* The file, after qlzx_hint_plan (item_rec .. totals = its outputs, on the device): head, items
+ * and index, totals[6,7] bytes from `out` on; chunk_id goes into every item (buildHintFromData
+ * passes 0).  `out` is 16-B aligned and need not be zeroed; no byte past the file's is written.
+ * If the file exceeds out_cap nothing is written and totals[8] = QLZX_HINT_NO_SPACE, else
+ * totals[8] = 0.  16 + 289 (n - first) bytes always suffice.  Whatever the plan arrays hold, every
+ * access stays inside data, the arrays' cap entries and out_cap.
+ * cap == 0 returns QLZX_R_OK; nothing is launched or written. */
+int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off, uint32_t cap, const int32_t *hdr,
+                    const uint16_t *vhash, uint32_t chunk_id, const uint32_t *item_rec, const uint64_t *item_hash,
+                    const uint64_t *item_off, const uint32_t *index_item, uint8_t *out, uint64_t out_cap,
+                    uint32_t *totals /* in/out */, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Getvhash (store/item.go:89-100, Fnv1a of utils/hash.go:8-16) of n values. */
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,
                      void *stream);
