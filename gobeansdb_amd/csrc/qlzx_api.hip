@@ -4,7 +4,9 @@
 // qlzx_decode_batch.hip, the single-call entry points in qlzx_single.hip.
 //
 // Unity build: the kernel sources are included here so the device tables
-// (qlzx_tables.hip) link without relocatable device code.
+// (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
+// (replay, read, write, gc, hint) share qlzx_recfile.h; read also uses replay's k_rp_crc_long,
+// ScatterComp and finish kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +49,21 @@ extern "C" int qlzx_profile_set(void *dev_buf) {  // g_prof of both translation 
     return qlzx::k2_profile_set(dev_buf);
 }
 #endif
+
+// What the record-file entry points (replay, read, write, gc, hint) repeat: `who` is the
+// function's name, the error text "<who>: <what>".
+static int fail_in(int code, const char *who, const char *what) {
+    return fail(code, (std::string(who) + ": " + what).c_str());
+}
+// slot numbers are 32 bits wide in the kernels
+static int check_chunk_size(const char *who, uint64_t size) {
+    return size / 256 >= 0xfffffff0ull ? fail_in(QLZX_R_BAD_ARG, who, "file too large") : QLZX_R_OK;
+}
+static int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, size_t need) {
+    return !workspace || workspace_bytes < need ? fail_in(QLZX_R_WORKSPACE, who, "workspace too small") : QLZX_R_OK;
+}
+// the tail of an entry point: e = what its launcher returned (a hipError_t)
+static int launched(const char *who, int e) { return e ? fail(QLZX_R_HIP, who, (hipError_t)e) : QLZX_R_OK; }
 
 extern "C" {
 
@@ -155,8 +172,9 @@ int qlzx_compress_batch(const qlzx_blocks *b, uint32_t *csize, int32_t *status,
     if (b->n == 0) return QLZX_R_OK;
     if (!b->src || !b->src_off || !b->src_len || !b->dst || !b->dst_off)
         return fail(QLZX_R_BAD_ARG, "qlzx_compress_batch: null block array");
-    if (workspace_bytes < qlzx_compress_workspace_size(b->n, max_len) || !workspace)
-        return fail(QLZX_R_WORKSPACE, "qlzx_compress_batch: workspace too small");
+    if (int r = check_workspace("qlzx_compress_batch", workspace, workspace_bytes,
+                                qlzx_compress_workspace_size(b->n, max_len)))
+        return r;
     hipStream_t s = (hipStream_t)stream;
     const bool wg = qlzx::encode_wg_enabled() && !(flags & QLZX_F_GO_COMPAT);
     const bool huge = max_len > QLZX_WG_MAX_LEN;  // values over 64 KiB: qlzx_encode_huge.hip
@@ -273,16 +291,13 @@ int qlzx_replay_index(const uint8_t *data, uint64_t size, uint64_t start, uint32
     if ((!data && size) || !rec_off || !rec_broken || !result)
         return fail(QLZX_R_BAD_ARG, "qlzx_replay_index: null arg");
     if (start % 256 != 0 || start > size) return fail(QLZX_R_BAD_ARG, "qlzx_replay_index: start not a slot");
-    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_replay_index: file too large");
-    if (!workspace || workspace_bytes < qlzx_replay_workspace_size(size))
-        return fail(QLZX_R_WORKSPACE, "qlzx_replay_index: workspace too small");
-    const int e = qlzx::launch_replay_index(data, size, start, max_key, body_max, rec_off, rec_broken, result,
-                                            workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_replay_index", (hipError_t)e);
-    return QLZX_R_OK;
+    if (int r = check_chunk_size("qlzx_replay_index", size)) return r;
+    if (int r = check_workspace("qlzx_replay_index", workspace, workspace_bytes, qlzx_replay_workspace_size(size))) return r;
+    return launched("qlzx_replay_index", qlzx::launch_replay_index(data, size, start, max_key, body_max, rec_off,
+                    rec_broken, result, workspace, (hipStream_t)stream));
 }
 
-size_t qlzx_replay_plan_workspace_size(uint32_t cap) { return qlzx::replay_plan_ws_bytes(cap); }
+size_t qlzx_replay_plan_workspace_size(uint32_t cap) { return qlzx::replay_plan_ws_layout(cap, nullptr, nullptr, nullptr); }
 
 int qlzx_replay_plan(const uint8_t *data, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
                      int32_t *hdr, uint32_t *comp_idx, uint64_t *comp_off, uint32_t *comp_len, uint32_t *comp_dsize,
@@ -290,12 +305,9 @@ int qlzx_replay_plan(const uint8_t *data, const uint64_t *rec_off, const uint32_
     if (!rec_off || !result || !hdr || !comp_idx || !comp_off || !comp_len || !comp_dsize || !comp_dst_off || !totals)
         return fail(QLZX_R_BAD_ARG, "qlzx_replay_plan: null arg");
     // data may be null for an empty chunk: nothing is read beyond result[0] = 0 records
-    if (!workspace || workspace_bytes < qlzx::replay_plan_ws_bytes(cap))
-        return fail(QLZX_R_WORKSPACE, "qlzx_replay_plan: workspace too small");
-    const int e = qlzx::launch_replay_plan(data, rec_off, result, cap, hdr, comp_idx, comp_off, comp_len, comp_dsize,
-                                           comp_dst_off, totals, workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_replay_plan", (hipError_t)e);
-    return QLZX_R_OK;
+    if (int r = check_workspace("qlzx_replay_plan", workspace, workspace_bytes, qlzx::replay_plan_ws_layout(cap, nullptr, nullptr, nullptr))) return r;
+    return launched("qlzx_replay_plan", qlzx::launch_replay_plan(data, rec_off, result, cap, hdr, comp_idx, comp_off,
+                    comp_len, comp_dsize, comp_dst_off, totals, workspace, (hipStream_t)stream));
 }
 
 int qlzx_replay_finish(const uint8_t *data, const uint64_t *rec_off, const uint32_t *result, const uint32_t *totals,
@@ -305,11 +317,9 @@ int qlzx_replay_finish(const uint8_t *data, const uint64_t *rec_off, const uint3
     if (!rec_off || !result || !totals || !comp_idx || !comp_status || !comp_dsize || !comp_dst_off || !flag ||
         !value_len || !in_out || !val_off || !vhash)
         return fail(QLZX_R_BAD_ARG, "qlzx_replay_finish: null arg");
-    const int e = qlzx::launch_replay_finish(data, rec_off, result, totals, comp_idx, comp_status, comp_dsize,
-                                             comp_dst_off, outbuf, cap, flag, value_len, in_out, val_off, vhash,
-                                             (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_replay_finish", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_replay_finish", qlzx::launch_replay_finish(data, rec_off, result, totals, comp_idx,
+                    comp_status, comp_dsize, comp_dst_off, outbuf, cap, flag, value_len, in_out, val_off, vhash,
+                    (hipStream_t)stream));
 }
 
 size_t qlzx_read_plan_workspace_size(uint32_t n) { return qlzx::read_ws_layout(n, nullptr, nullptr); }
@@ -328,17 +338,14 @@ int qlzx_read_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, 
         if (nkeys != 0 && nkeys != 3) return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: want_key* are all three or none");
         if ((nkeys == 3) != (key_eq != nullptr))
             return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: key_eq goes with the wanted keys");
-        if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: file too large");
+        if (int r = check_chunk_size("qlzx_read_plan", size)) return r;
         if (body_max > 0xffffffffull - 24 - max_key)
             return fail(QLZX_R_BAD_ARG, "qlzx_read_plan: 24 + max_key + body_max is 4 GiB or more");
-        if (!workspace || workspace_bytes < qlzx_read_plan_workspace_size(n))
-            return fail(QLZX_R_WORKSPACE, "qlzx_read_plan: workspace too small");
+        if (int r = check_workspace("qlzx_read_plan", workspace, workspace_bytes, qlzx_read_plan_workspace_size(n))) return r;
     }
-    const int e = qlzx::launch_read_plan(data, size, rec_off, n, max_key, body_max, want_key, want_key_off,
-                                         want_key_len, rd_status, key_eq, hdr, comp_idx, comp_off, comp_len,
-                                         comp_dsize, comp_dst_off, totals, workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_read_plan", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_read_plan", qlzx::launch_read_plan(data, size, rec_off, n, max_key, body_max, want_key,
+                    want_key_off, want_key_len, rd_status, key_eq, hdr, comp_idx, comp_off, comp_len, comp_dsize,
+                    comp_dst_off, totals, workspace, (hipStream_t)stream));
 }
 
 int qlzx_read_finish(const uint8_t *data, const uint64_t *rec_off, uint32_t n, const int32_t *rd_status,
@@ -351,11 +358,9 @@ int qlzx_read_finish(const uint8_t *data, const uint64_t *rec_off, uint32_t n, c
     if (!rec_off || !rd_status || !totals || !comp_idx || !comp_status || !comp_dsize || !comp_dst_off || !flag ||
         !value_len || !in_out || !val_off || !vhash || !dec_status)
         return fail(QLZX_R_BAD_ARG, "qlzx_read_finish: null arg");
-    const int e = qlzx::launch_read_finish(data, rec_off, n, rd_status, totals, comp_idx, comp_status, comp_dsize,
-                                           comp_dst_off, outbuf, flag, value_len, in_out, val_off, vhash, dec_status,
-                                           (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_read_finish", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_read_finish", qlzx::launch_read_finish(data, rec_off, n, rd_status, totals, comp_idx,
+                    comp_status, comp_dsize, comp_dst_off, outbuf, flag, value_len, in_out, val_off, vhash,
+                    dec_status, (hipStream_t)stream));
 }
 
 size_t qlzx_write_plan_workspace_size(uint32_t n) { return qlzx::write_ws_layout(n, nullptr, nullptr); }
@@ -372,14 +377,11 @@ int qlzx_write_plan(const uint8_t *values, const uint64_t *val_off, const uint32
             return fail(QLZX_R_BAD_ARG, "qlzx_write_plan: null arg");
         if (body_max > 0xffffffffull - 24 - 9 - 256 - max_key)
             return fail(QLZX_R_BAD_ARG, "qlzx_write_plan: 24 + max_key + body_max + 9 + 256 is 4 GiB or more");
-        if (!workspace || workspace_bytes < qlzx_write_plan_workspace_size(n))
-            return fail(QLZX_R_WORKSPACE, "qlzx_write_plan: workspace too small");
+        if (int r = check_workspace("qlzx_write_plan", workspace, workspace_bytes, qlzx_write_plan_workspace_size(n))) return r;
     }
-    const int e = qlzx::launch_write_plan(values, val_off, val_len, key_len, flag, ver, n, max_key, body_max,
-                                          not_compress, wr_status, try_idx, try_off, try_len, try_dst_off, totals,
-                                          workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_write_plan", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_write_plan", qlzx::launch_write_plan(values, val_off, val_len, key_len, flag, ver, n,
+                    max_key, body_max, not_compress, wr_status, try_idx, try_off, try_len, try_dst_off, totals,
+                    workspace, (hipStream_t)stream));
 }
 
 int qlzx_write_decide(const uint64_t *val_off, const uint32_t *val_len, uint32_t n, const uint32_t *totals,
@@ -392,14 +394,11 @@ int qlzx_write_decide(const uint64_t *val_off, const uint32_t *val_len, uint32_t
         if (!val_off || !val_len || !totals || !try_idx || !try_len || !try_csize || !try_status || !keep ||
             !full_idx || !full_off || !full_len || !full_dst_off)
             return fail(QLZX_R_BAD_ARG, "qlzx_write_decide: null arg");
-        if (!workspace || workspace_bytes < qlzx_write_plan_workspace_size(n))
-            return fail(QLZX_R_WORKSPACE, "qlzx_write_decide: workspace too small");
+        if (int r = check_workspace("qlzx_write_decide", workspace, workspace_bytes, qlzx_write_plan_workspace_size(n))) return r;
     }
-    const int e = qlzx::launch_write_decide(val_off, val_len, n, totals, try_idx, try_len, try_csize, try_status, keep,
-                                            full_idx, full_off, full_len, full_dst_off, totals2, workspace,
-                                            (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_write_decide", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_write_decide", qlzx::launch_write_decide(val_off, val_len, n, totals, try_idx, try_len,
+                    try_csize, try_status, keep, full_idx, full_off, full_len, full_dst_off, totals2, workspace,
+                    (hipStream_t)stream));
 }
 
 int qlzx_write_finish(const uint8_t *values, const uint64_t *val_off, const uint32_t *val_len, const uint8_t *keys,
@@ -421,16 +420,13 @@ int qlzx_write_finish(const uint8_t *values, const uint64_t *val_off, const uint
             !flag_out || !vsz || !crc)
             return fail(QLZX_R_BAD_ARG, "qlzx_write_finish: null arg");
         if ((uintptr_t)out & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_write_finish: out is not 16-B aligned");
-        if (!workspace || workspace_bytes < qlzx_write_plan_workspace_size(n))
-            return fail(QLZX_R_WORKSPACE, "qlzx_write_finish: workspace too small");
+        if (int r = check_workspace("qlzx_write_finish", workspace, workspace_bytes, qlzx_write_plan_workspace_size(n))) return r;
     }
     const qlzx::WrFinishArgs a{values,  keys,       trial_buf, full_buf, val_off,   key_off,  try_dst_off, full_dst_off,
                                val_len, key_len,    flag,      ts,       totals,    try_idx,  try_len,     try_csize,
                                try_crc, totals2,    full_idx,  full_csize, full_crc, ver,     full_status, keep};
-    const int e = qlzx::launch_write_finish(a, n, out, out_cap, wr_status, rec_off, flag_out, vsz, crc, vhash, totals3,
-                                            workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_write_finish", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_write_finish", qlzx::launch_write_finish(a, n, out, out_cap, wr_status, rec_off, flag_out,
+                    vsz, crc, vhash, totals3, workspace, (hipStream_t)stream));
 }
 
 size_t qlzx_gc_workspace_size(uint32_t cap, uint32_t max_chunks) {
@@ -448,16 +444,13 @@ int qlzx_gc_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, co
         return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: null arg");
     if (max_chunks < 1 || max_chunks > 998) return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: max_chunks is 1 to 998");
     if ((uintptr_t)data & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: data is not 16-B aligned");
-    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: file too large");
+    if (int r = check_chunk_size("qlzx_gc_plan", size)) return r;
     if (body_max > 0xffffffffull - 24 - 256 - max_key)
         return fail(QLZX_R_BAD_ARG, "qlzx_gc_plan: 24 + max_key + body_max + 256 is 4 GiB or more");
-    if (!workspace || workspace_bytes < qlzx_gc_workspace_size(cap, max_chunks))
-        return fail(QLZX_R_WORKSPACE, "qlzx_gc_plan: workspace too small");
-    const int e = qlzx::launch_gc_plan(data, size, rec_off, result, cap, keep, max_key, body_max, data_file_max,
-                                       chunk_head, max_chunks, gc_status, new_chunk, new_off, chunk_base, chunk_bytes,
-                                       totals, workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_gc_plan", (hipError_t)e);
-    return QLZX_R_OK;
+    if (int r = check_workspace("qlzx_gc_plan", workspace, workspace_bytes, qlzx_gc_workspace_size(cap, max_chunks))) return r;
+    return launched("qlzx_gc_plan", qlzx::launch_gc_plan(data, size, rec_off, result, cap, keep, max_key, body_max,
+                    data_file_max, chunk_head, max_chunks, gc_status, new_chunk, new_off, chunk_base, chunk_bytes,
+                    totals, workspace, (hipStream_t)stream));
 }
 
 int qlzx_gc_rewrite(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
@@ -475,19 +468,17 @@ int qlzx_gc_rewrite(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
     // records are written in parallel: a chunk cannot be rewritten onto itself
     if (size && out_cap && (uintptr_t)out < (uintptr_t)data + size && (uintptr_t)data < (uintptr_t)out + out_cap)
         return fail(QLZX_R_BAD_ARG, "qlzx_gc_rewrite: out overlaps data");
-    if (!workspace || workspace_bytes < qlzx_gc_workspace_size(cap, max_chunks))
-        return fail(QLZX_R_WORKSPACE, "qlzx_gc_rewrite: workspace too small");
+    if (int r = check_workspace("qlzx_gc_rewrite", workspace, workspace_bytes, qlzx_gc_workspace_size(cap, max_chunks))) return r;
     const qlzx::GcIn in{data, size, rec_off, chunk_head, new_off, chunk_base, new_chunk, max_chunks, out, out_cap};
-    const int e = qlzx::launch_gc_rewrite(in, result, cap, gc_status, crc, totals, workspace, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_gc_rewrite", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_gc_rewrite", qlzx::launch_gc_rewrite(in, result, cap, gc_status, crc, totals, workspace,
+                    (hipStream_t)stream));
 }
 
 int qlzx_keyhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint64_t *out,
                        void *stream) {
     if (n == 0) return QLZX_R_OK;
     if (!src || !off || !len || !out) return fail(QLZX_R_BAD_ARG, "qlzx_keyhash_batch: null arg");
-    hipLaunchKernelGGL(qlzx::k_keyhash, dim3(qlzx::hint_grid(n)), dim3(256), 0, (hipStream_t)stream, src, off, len, n,
+    hipLaunchKernelGGL(qlzx::k_keyhash, dim3(qlzx::grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, src, off, len, n,
                        out);
     HIP_OK(hipGetLastError());
     return QLZX_R_OK;
@@ -506,15 +497,12 @@ int qlzx_hint_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, 
         !totals)
         return fail(QLZX_R_BAD_ARG, "qlzx_hint_plan: null arg");
     if (split_cap == 0) return fail(QLZX_R_BAD_ARG, "qlzx_hint_plan: split_cap is 1 or more");
-    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_hint_plan: file too large");
-    if (!workspace || workspace_bytes < qlzx_hint_workspace_size(cap))
-        return fail(QLZX_R_WORKSPACE, "qlzx_hint_plan: workspace too small");
+    if (int r = check_chunk_size("qlzx_hint_plan", size)) return r;
+    if (int r = check_workspace("qlzx_hint_plan", workspace, workspace_bytes, qlzx_hint_workspace_size(cap))) return r;
     const qlzx::HintIn in{data, size, rec_off, hdr, cap};
-    const int e = qlzx::launch_hint_plan(in, result, keyhash, first, split_cap, index_interval, max_offset_in,
-                                         item_rec, item_hash, item_off, index_item, totals, workspace,
-                                         (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_hint_plan", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_hint_plan", qlzx::launch_hint_plan(in, result, keyhash, first, split_cap, index_interval,
+                    max_offset_in, item_rec, item_hash, item_off, index_item, totals, workspace,
+                    (hipStream_t)stream));
 }
 
 int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off, uint32_t cap, const int32_t *hdr,
@@ -526,16 +514,13 @@ int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
         (!out && out_cap) || !totals)
         return fail(QLZX_R_BAD_ARG, "qlzx_hint_write: null arg");
     if ((uintptr_t)out & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_hint_write: out is not 16-B aligned");
-    if (size / 256 >= 0xfffffff0ull) return fail(QLZX_R_BAD_ARG, "qlzx_hint_write: file too large");
-    if (!workspace || workspace_bytes < qlzx_hint_workspace_size(cap))
-        return fail(QLZX_R_WORKSPACE, "qlzx_hint_write: workspace too small");
+    if (int r = check_chunk_size("qlzx_hint_write", size)) return r;
+    if (int r = check_workspace("qlzx_hint_write", workspace, workspace_bytes, qlzx_hint_workspace_size(cap))) return r;
     qlzx::HintFile f{};
     f.in = qlzx::HintIn{data, size, rec_off, hdr, cap};
     f.vhash = vhash, f.item_rec = item_rec, f.index_item = index_item, f.item_hash = item_hash, f.item_off = item_off;
     f.chunk_id = chunk_id;
-    const int e = qlzx::launch_hint_write(f, out, out_cap, totals, (hipStream_t)stream);
-    if (e) return fail(QLZX_R_HIP, "qlzx_hint_write", (hipError_t)e);
-    return QLZX_R_OK;
+    return launched("qlzx_hint_write", qlzx::launch_hint_write(f, out, out_cap, totals, (hipStream_t)stream));
 }
 
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,

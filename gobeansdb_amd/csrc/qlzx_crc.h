@@ -91,6 +91,27 @@ __device__ __forceinline__ uint32_t crc_mul_tab(const uint32_t *m, uint32_t c) {
     return m[c & 0xffu] ^ m[256 + ((c >> 8) & 0xffu)] ^ m[512 + ((c >> 16) & 0xffu)] ^ m[768 + (c >> 24)];
 }
 
+// The 64 lane registers of the stripe layout merged in a 6-level tree (level k shifts over the
+// 64 * 2^k bytes of the lanes it absorbs: mul = the g_crc_mul tables); every lane returns lane 0's.
+__device__ __forceinline__ uint32_t crc_lane_merge(const uint32_t *mul, uint32_t c) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) c = crc_mul_tab(mul + k * 1024, c) ^ __shfl_xor(c, 1 << k, 64);
+    return __shfl(c, 0, 64);
+}
+
+// A 16-B chunk of a record image stored at d (16-B aligned).  Of the record's first chunk only
+// dwords 1..3 go out now: its CRC word, dword 0, is stored last, by whoever finishes the CRC.
+// (gc_span states the same store in its own loop: through this helper its next-stripe loads were
+// no longer issued ahead of the CRC, and the GC copy of 4-64 KiB records took twice as long.)
+__device__ __forceinline__ void store_rec_chunk(uint8_t *d, uint4 v, bool first) {
+    if (first) {
+        uint32_t *w = (uint32_t *)d;
+        w[1] = v.y, w[2] = v.z, w[3] = v.w;
+    } else {
+        *(uint4 *)d = v;
+    }
+}
+
 // CRC register after the len bytes at p from state init (no final inversion); every lane
 // returns it.  lds = load_crc_lds's tables.  p need not be aligned: the dword view starts at
 // p rounded down, the m = p % 4 bytes before p are masked to zero.
@@ -141,9 +162,7 @@ __device__ uint32_t wave_crc(const uint32_t *lds, const uint8_t *p, uint64_t len
 #pragma unroll
         for (int k = 0; k < 16; k += 2) c = crc_slice8(t8, c, w[k], w[k + 1]);
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) c = crc_mul_tab(mul + k * 1024, c) ^ __shfl_xor(c, 1 << k, 64);
-    return __shfl(c, 0, 64);
+    return crc_lane_merge(mul, c);
 }
 
 // ---- wave_crc_rep: wave_crc with the byte table replicated across LDS banks ----
@@ -222,9 +241,7 @@ __device__ __forceinline__ uint32_t wave_crc_rep(const uint32_t *tab, const uint
         }
         c = crc_mul_tab(g_crc_mul32, c) ^ d;
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) c = crc_mul_tab(mul + k * 1024, c) ^ __shfl_xor(c, 1 << k, 64);
-    return __shfl(c, 0, 64);
+    return crc_lane_merge(mul, c);
 }
 
 }  // namespace qlzx

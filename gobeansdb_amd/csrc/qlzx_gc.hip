@@ -8,7 +8,7 @@
 // DataFileMax (store/gc.go:320-336).
 //
 // Two calls, nothing read back in between:
-//   plan     k_gc_check: readRecordAt's size checks (k_rd_check's, without the CRC) on every kept
+//   plan     k_gc_check: readRecordAt's size checks (qlzx_recfile.h; no CRC) on every kept
 //            record and its padded size; k_rp_dstoff: the u64 exclusive scan S of the sizes;
 //            k_gc_cut: the rotation is a greedy cut of S, one wave finds each destination chunk's
 //            first record by a 64-way search over S; k_gc_place: (chunk, offset) per record;
@@ -16,8 +16,8 @@
 //            and destination both start on 256-B boundaries), computes the CRC in the same pass
 //            (wave_crc's stripe layout, anchored at the end of the span as wr_span's) and writes
 //            them with aligned 16-B stores, padding included, the CRC word last; records with a
-//            CRC span over kRpLong are cut into kRpSeg segments over the chip (k_gc_long).
-#include "qlzx_device.h"
+//            CRC span over kRpLong are cut into kRpSeg segments over the chip (k_rec_long<GcLong>).
+#include "qlzx_recfile.h"
 
 namespace qlzx {
 
@@ -27,11 +27,6 @@ struct GcCounters {
     uint32_t t5[6];  // k_rp_dstoff's totals; pads the struct to a multiple of 16 bytes
 };
 
-__device__ __forceinline__ uint32_t gc_count(const uint32_t *result, uint32_t cap) {
-    const uint32_t n = result[0];
-    return n < cap ? n : cap;
-}
-
 // ---- plan ----
 // Per record: DROPPED, BAD_RECORD or WRITTEN (so far: the cut may still say NO_CHUNK), and
 // sz[j] = its padded size, 0 for a record that takes no space.
@@ -39,7 +34,7 @@ __global__ void __launch_bounds__(256) k_gc_check(const uint8_t *data, uint64_t 
                                                   const uint32_t *result, uint32_t cap, const uint8_t *keep,
                                                   uint32_t max_key, uint64_t body_max, int32_t *gc_status,
                                                   uint32_t *sz, GcCounters *cnt) {
-    const uint32_t n = gc_count(result, cap);
+    const uint32_t n = rec_count(result, cap);
     uint32_t nkeep = 0, nbad = 0;
     for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
         int32_t st = QLZX_GC_DROPPED;
@@ -48,12 +43,11 @@ __global__ void __launch_bounds__(256) k_gc_check(const uint8_t *data, uint64_t 
             nkeep++;
             st = QLZX_GC_BAD_RECORD;
             const uint64_t off = rec_off[j];
-            if (off % kRpSlot == 0 && off <= size && size - off >= kRpHdr) {
+            if (rec_pos_verdict(off, size) == kRecOk) {
                 const uint2 kv = *(const uint2 *)(data + off + 16);  // ksz, vsz
-                if (kv.x != 0 && kv.x <= max_key && (uint64_t)kv.y <= body_max &&
-                    size - off - kRpHdr >= (uint64_t)kv.x + kv.y) {
+                if (rec_size_verdict(kv.x, kv.y, size - off - kRpHdr, max_key, body_max) == kRecOk) {
                     st = QLZX_GC_WRITTEN;
-                    s = (uint32_t)wr_pad256((uint64_t)kRpHdr + kv.x + kv.y);
+                    s = (uint32_t)pad256((uint64_t)kRpHdr + kv.x + kv.y);
                 }
             }
             nbad += st == QLZX_GC_BAD_RECORD;
@@ -61,10 +55,7 @@ __global__ void __launch_bounds__(256) k_gc_check(const uint8_t *data, uint64_t 
         gc_status[j] = st;
         sz[j] = s;
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        nkeep += __shfl_xor(nkeep, m, 64);
-        nbad += __shfl_xor(nbad, m, 64);
-    }
+    nkeep = wave_sum(nkeep), nbad = wave_sum(nbad);
     if ((threadIdx.x & 63) == 0) {
         if (nkeep) atomicAdd(&cnt->nkeep, nkeep);
         if (nbad) atomicAdd(&cnt->nbad, nbad);
@@ -162,10 +153,7 @@ __global__ void __launch_bounds__(256) k_gc_place(const uint64_t *S, const uint3
         new_chunk[j] = c;
         new_off[j] = o;
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        nplaced += __shfl_xor(nplaced, m, 64);
-        nnochunk += __shfl_xor(nnochunk, m, 64);
-    }
+    nplaced = wave_sum(nplaced), nnochunk = wave_sum(nnochunk);
     if ((threadIdx.x & 63) == 0) {
         if (nplaced) atomicAdd(&cnt->nplaced, nplaced);
         if (nnochunk) atomicAdd(&cnt->nnochunk, nnochunk);
@@ -222,7 +210,7 @@ __device__ uint32_t gc_span(const uint32_t *lds, const uint8_t *src, uint8_t *ds
             const int64_t xc = p + 16 * k;
             if (xc < (int64_t)r0) continue;
             uint32_t *d = (uint32_t *)(dst + xc);
-            if (xc == 0) {  // the CRC word comes last; the initial state goes over dword 1
+            if (xc == 0) {  // the CRC word comes last (as store_rec_chunk); the initial state goes over dword 1
                 d[1] = v[k].y, d[2] = v[k].z, d[3] = v[k].w;
                 v[k].x = 0;
                 v[k].y ^= 0xffffffffu;
@@ -236,9 +224,7 @@ __device__ uint32_t gc_span(const uint32_t *lds, const uint8_t *src, uint8_t *ds
             c = crc_slice8(t8, c, v[k].z, v[k].w);
         }
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) c = crc_mul_tab(mul + k * 1024, c) ^ __shfl_xor(c, 1 << k, 64);
-    return __shfl(c, 0, 64);
+    return crc_lane_merge(mul, c);
 }
 
 // The record's last bytes src[e16, end), fewer than 16, as four dwords (zeros past the end); never
@@ -335,7 +321,7 @@ __device__ __forceinline__ GcRec gc_rec(const GcIn &in, const GcIdx &I, const Gc
     const uint64_t end = (uint64_t)kRpHdr + H.ksz + H.vsz;
     if (H.ksz == 0 || end > R.avail || end > 0xffffff00ull) return R;
     R.end = (uint32_t)end;
-    R.rsz = (uint32_t)wr_pad256(end);
+    R.rsz = (uint32_t)pad256(end);
     const uint64_t pos = H.cbase + (I.noff - H.chead);
     R.st = QLZX_GC_NO_SPACE;
     if (pos % kRpSlot != 0 || pos > in.out_cap || in.out_cap - pos < R.rsz) return R;
@@ -346,16 +332,15 @@ __device__ __forceinline__ GcRec gc_rec(const GcIn &in, const GcIdx &I, const Gc
 
 // k_gc_copy: a wave per record, grid-stride.  A record that would end past out_cap gets
 // QLZX_GC_NO_SPACE and nothing of it is written; one whose CRC span exceeds kRpLong goes to the
-// k_gc_long list.  What leads to a record's bytes is two dependent loads deep (its array entries,
+// long list (k_rec_long<GcLong>).  What leads to a record's bytes is two dependent loads deep (its array entries,
 // then its header and chunk), so a wave loads the entries of its record after next and the header
 // of its next record before it copies the current one: in the steady state a record waits for its
 // own bytes only.
 __global__ void __launch_bounds__(256) k_gc_copy(GcIn in, const uint32_t *result, uint32_t cap, int32_t *gc_status,
-                                                 uint32_t *crc, GcCounters *cnt, uint32_t *lng, uint32_t *lacc,
-                                                 uint32_t *ldone) {
+                                                 uint32_t *crc, GcCounters *cnt, LongList ll) {
     __shared__ uint32_t tab[kCrcLdsWords];
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t n = gc_count(result, cap);
+    const uint32_t n = rec_count(result, cap);
     const uint32_t j0 = blockIdx.x * 4 + threadIdx.x / 64, stride = gridDim.x * 4;
     GcIdx I0 = gc_idx(in, gc_status, j0, n), I1 = gc_idx(in, gc_status, j0 + stride, n);
     GcHdr H0 = gc_hdr(in, I0);
@@ -382,12 +367,7 @@ __global__ void __launch_bounds__(256) k_gc_copy(GcIn in, const uint32_t *result
             continue;
         }
         if (R.end - 4 > kRpLong) {
-            if (lane == 0) {
-                const uint32_t e = atomicAdd(&cnt->nlong, 1u);
-                lng[e] = j;
-                lacc[e] = 0;
-                ldone[e] = 0;
-            }
+            if (lane == 0) ll.push(j);
             continue;
         }
         const uint32_t e16 = R.end & ~15u;
@@ -409,53 +389,32 @@ __global__ void __launch_bounds__(256) k_gc_copy(GcIn in, const uint32_t *result
     }
 }
 
-// long records, as k_wr_long: every wave takes the segments g of the global segment sequence with
-// g = wave id (mod all waves).  Segment r of a record is its bytes [r kRpSeg, (r + 1) kRpSeg) (the
-// last one runs to the record's end and writes the tail and the padding); its raw CRC, shifted
-// over the bytes after it, is XORed into the record's accumulator, and the wave that completes
-// the last segment writes the CRC word.
-__global__ void __launch_bounds__(256) k_gc_long(GcIn in, uint32_t *crc, GcCounters *cnt, const uint32_t *lng,
-                                                 uint32_t *lacc, uint32_t *ldone) {
-    __shared__ uint32_t tab[kCrcLdsWords];
-    const uint32_t nl = cnt->nlong;
-    if (nl == 0) return;
-    load_crc_lds(tab);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wid = blockIdx.x * 4 + threadIdx.x / 64, nw = gridDim.x * 4;
-    uint64_t g = 0;
-    for (uint32_t e = 0; e < nl; e++) {
-        const uint32_t j = lng[e];
+// k_rec_long's policy: a long record's segments are spans of its source bytes, the last one with
+// the tail (loaded before the span runs, as in k_gc_copy).
+struct GcLong {
+    GcIn in;
+    uint32_t *crc, *nmis;
+    using Rec = GcRec;
+    __device__ Rec rec(uint32_t j) const {
         GcIdx I;  // k_gc_copy lists WRITTEN records only
         I.st = QLZX_GC_WRITTEN, I.c = in.new_chunk[j], I.off = in.rec_off[j], I.noff = in.new_off[j];
-        const GcRec R = gc_rec(in, I, gc_hdr(in, I));
-        if (R.st != QLZX_GC_WRITTEN) continue;  // k_gc_copy listed it: the same answer here
-        const uint32_t e16 = R.end & ~15u;
-        const uint32_t nseg = (e16 + kRpSeg - 1) / kRpSeg;
-        for (uint32_t r = (uint32_t)((wid + nw - g % nw) % nw); r < nseg; r += nw) {
-            const uint32_t r0 = r * kRpSeg;
-            const bool last = r == nseg - 1;
-            const uint32_t r1 = last ? e16 : r0 + kRpSeg;
-            uint4 tail = make_uint4(0, 0, 0, 0);
-            if (last) tail = gc_tail_load(R.src, R.avail, e16, R.end);
-            uint32_t reg = gc_span(tab, R.src, R.dst, r0, r1, lane);
-            if (last) reg = gc_tail(tab, tail, R.dst, e16, R.end, R.rsz, reg, lane);
-            else reg = crc_shift(reg, R.end - r1);
-            if (lane == 0) {
-                atomicXor(&lacc[e], reg);
-                __threadfence();
-                if (atomicAdd(&ldone[e], 1u) == nseg - 1) {
-                    __threadfence();
-                    const uint32_t sum = ~atomicOr(&lacc[e], 0u);
-                    *(uint32_t *)R.dst = sum;
-                    crc[j] = sum;
-                    if (sum != R.stored) atomicAdd(&cnt->nmis, 1u);
-                }
-            }
-        }
-        g += nseg;
+        return gc_rec(in, I, gc_hdr(in, I));
     }
-}
+    __device__ bool valid(const Rec &R) const { return R.st == QLZX_GC_WRITTEN; }  // k_gc_copy's answer again
+    __device__ uint32_t end(const Rec &R) const { return R.end; }
+    __device__ uint32_t segment(const uint32_t *lds, const Rec &R, uint32_t r0, uint32_t r1, bool last,
+                                uint32_t lane) const {
+        uint4 tail = make_uint4(0, 0, 0, 0);
+        if (last) tail = gc_tail_load(R.src, R.avail, r1, R.end);
+        const uint32_t reg = gc_span(lds, R.src, R.dst, r0, r1, lane);
+        return last ? gc_tail(lds, tail, R.dst, r1, R.end, R.rsz, reg, lane) : reg;
+    }
+    __device__ void finish(uint32_t j, const Rec &R, uint32_t sum) const {
+        *(uint32_t *)R.dst = ~sum;
+        crc[j] = ~sum;
+        if (~sum != R.stored) atomicAdd(nmis, 1u);
+    }
+};
 
 __global__ void k_gc_totals2(uint32_t *totals, const uint32_t *result, const GcCounters *cnt) {
     if (result[0] == 0) {
@@ -477,22 +436,17 @@ struct GcWs {
     uint64_t *S;
 };
 inline size_t gc_ws_layout(uint32_t cap, uint32_t max_chunks, uint8_t *base, GcWs *w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t *p = base ? base + o : nullptr;
-        o += rp_align(bytes);
-        return p;
-    };
+    WsCarver c{base};
     GcWs t;
-    t.cnt = (GcCounters *)take(sizeof(GcCounters));
-    t.sz = (uint32_t *)take(4 * (size_t)cap);
-    t.first = (uint32_t *)take(4 * ((size_t)max_chunks + 1));
-    t.lng = (uint32_t *)take(4 * (size_t)cap);
-    t.lacc = (uint32_t *)take(4 * (size_t)cap);
-    t.ldone = (uint32_t *)take(4 * (size_t)cap);
-    t.S = (uint64_t *)take(8 * (size_t)cap);
+    t.cnt = c.take<GcCounters>(sizeof(GcCounters));
+    t.sz = c.take<uint32_t>(4 * (size_t)cap);
+    t.first = c.take<uint32_t>(4 * ((size_t)max_chunks + 1));
+    t.lng = c.take<uint32_t>(4 * (size_t)cap);
+    t.lacc = c.take<uint32_t>(4 * (size_t)cap);
+    t.ldone = c.take<uint32_t>(4 * (size_t)cap);
+    t.S = c.take<uint64_t>(8 * (size_t)cap);
     if (w) *w = t;
-    return o;
+    return c.bytes();
 }
 
 inline int launch_gc_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result,
@@ -504,7 +458,7 @@ inline int launch_gc_plan(const uint8_t *data, uint64_t size, const uint64_t *re
     gc_ws_layout(cap, max_chunks, (uint8_t *)ws, &w);
     const hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(GcCounters), s);
     if (e != hipSuccess) return (int)e;
-    const uint32_t grid = wr_grid(cap);
+    const uint32_t grid = grid_for(cap);
     hipLaunchKernelGGL(k_gc_check, dim3(grid), dim3(256), 0, s, data, size, rec_off, result, cap, keep, max_key,
                        body_max, gc_status, w.sz, w.cnt);
     // S: the exclusive scan of the padded sizes (0 for a record that takes no space)
@@ -524,10 +478,10 @@ inline int launch_gc_rewrite(const GcIn &in, const uint32_t *result, uint32_t ca
     gc_ws_layout(cap, in.max_chunks, (uint8_t *)ws, &w);
     const hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(GcCounters), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_gc_copy, dim3(std::min<uint32_t>((cap + 3) / 4, 2048)), dim3(256), 0, s, in, result, cap,
-                       gc_status, crc, w.cnt, w.lng, w.lacc, w.ldone);
-    hipLaunchKernelGGL(k_gc_long, dim3(2048), dim3(256), 0, s, in, crc, w.cnt, (const uint32_t *)w.lng, w.lacc,
-                       w.ldone);
+    const LongList ll{&w.cnt->nlong, w.lng, w.lacc, w.ldone};
+    hipLaunchKernelGGL(k_gc_copy, dim3(grid_for(cap, 4, 2048)), dim3(256), 0, s, in, result, cap, gc_status, crc,
+                       w.cnt, ll);
+    hipLaunchKernelGGL(k_rec_long<GcLong>, dim3(2048), dim3(256), 0, s, GcLong{in, crc, &w.cnt->nmis}, ll);
     hipLaunchKernelGGL(k_gc_totals2, dim3(1), dim3(1), 0, s, totals, result, (const GcCounters *)w.cnt);
     return (int)hipGetLastError();
 }

@@ -20,7 +20,7 @@
 //          fields and the key bytes and stored with one aligned 16-B store.
 #include <rocprim/rocprim.hpp>
 
-#include "qlzx_device.h"
+#include "qlzx_recfile.h"
 
 namespace qlzx {
 
@@ -139,7 +139,7 @@ __device__ int hint_key_cmp(const uint8_t *a, uint32_t na, const uint8_t *b, uin
 // t = j - first over [0, M): vf[t] = record j is in range and passes the guards, hash[t] its keyhash.
 __global__ void __launch_bounds__(256) k_hint_hash(HintIn in, const uint32_t *result, const uint64_t *keyhash,
                                                    uint32_t first, uint32_t M, uint64_t *hash, uint32_t *vf) {
-    const uint32_t n = gc_count(result, in.cap);
+    const uint32_t n = rec_count(result, in.cap);
     for (uint32_t t = blockIdx.x * 256 + threadIdx.x; t < M; t += gridDim.x * 256) {
         const uint32_t j = first + t;
         uint32_t ok = 0;
@@ -259,7 +259,7 @@ __device__ __forceinline__ uint32_t hint_cut(const HintCounters *cnt, uint32_t n
 __global__ void __launch_bounds__(256) k_hint_items(HintIn in, const uint32_t *result, const uint8_t *gh,
                                                     const uint32_t *val_r, uint32_t M, HintAcc *itemv,
                                                     HintCounters *cnt) {
-    const uint32_t n = gc_count(result, in.cap), nv = cnt->nv, c = hint_cut(cnt, n);
+    const uint32_t n = rec_count(result, in.cap), nv = cnt->nv, c = hint_cut(cnt, n);
     uint32_t dmax = 0, nbelow = 0;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
         HintAcc v{0, 0};
@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(256) k_hint_items(HintIn in, const uint32_t *r
             const uint32_t r = val_r[i];
             if (r < c) {
                 const uint32_t ksz = (uint32_t)in.hdr[6 * (size_t)r + 4], vsz = (uint32_t)in.hdr[6 * (size_t)r + 5];
-                const uint32_t end = (uint32_t)in.rec_off[r] + (uint32_t)wr_pad256((uint64_t)kRpHdr + ksz + vsz);
+                const uint32_t end = (uint32_t)in.rec_off[r] + (uint32_t)pad256((uint64_t)kRpHdr + ksz + vsz);
                 dmax = max(dmax, end);
                 nbelow++;
                 if (i + 1 == nv || gh[i + 1] || val_r[i + 1] >= c) v = HintAcc{kHintItem + ksz, 1};
@@ -275,10 +275,8 @@ __global__ void __launch_bounds__(256) k_hint_items(HintIn in, const uint32_t *r
         }
         itemv[i] = v;
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        dmax = max(dmax, (uint32_t)__shfl_xor(dmax, m, 64));
-        nbelow += __shfl_xor(nbelow, m, 64);
-    }
+    for (int m = 32; m >= 1; m >>= 1) dmax = max(dmax, (uint32_t)__shfl_xor(dmax, m, 64));
+    nbelow = wave_sum(nbelow);
     if ((threadIdx.x & 63) == 0 && nbelow) {
         atomicMax(&cnt->datasize, dmax);
         atomicAdd(&cnt->nbelow, nbelow);
@@ -341,7 +339,7 @@ __global__ void __launch_bounds__(256) k_hint_index(const uint32_t *iflag, const
 
 __global__ void k_hint_totals(const uint64_t *rec_off, const uint32_t *result, uint32_t cap, uint32_t first,
                               uint32_t max_offset_in, uint32_t *totals, const HintCounters *cnt) {
-    const uint32_t n = gc_count(result, cap);
+    const uint32_t n = rec_count(result, cap);
     uint32_t consumed = 0, skipped = 0, nk = 0, nidx = 0, datasize = max_offset_in;
     uint64_t io = kHintHead;
     if (cnt) {  // cnt == nullptr: no record in range
@@ -523,34 +521,27 @@ inline size_t hint_ws_layout(uint32_t cap, uint8_t *base, HintWs *w) {
                                       q, HintAccPlus());
         tmp_bytes = std::max(tmp_bytes, std::max(std::max(sort_tmp, scan_tmp), acc_tmp));
     }
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t *p = base ? base + o : nullptr;
-        o += rp_align(bytes);
-        return p;
-    };
+    WsCarver c{base};
     HintWs t;
-    t.cnt = (HintCounters *)take(sizeof(HintCounters));
-    t.hash = (uint64_t *)take(16 * m);
+    t.cnt = c.take<HintCounters>(sizeof(HintCounters));
+    t.hash = c.take<uint64_t>(16 * m);
     t.key_in = t.hash ? t.hash + m : nullptr;
     t.itemv = (HintAcc *)t.hash;
-    t.items = (HintAcc *)take(16 * m);
-    t.key_s = (uint64_t *)take(8 * m);
-    t.val_in = (uint32_t *)take(4 * m);
-    t.val_s = (uint32_t *)take(4 * m);
-    t.val_r = (uint32_t *)take(4 * m);
-    t.list = (uint32_t *)take(4 * m);
-    t.fa = (uint32_t *)take(4 * m);
-    t.fb = (uint32_t *)take(4 * m);
-    t.fl = take(m);
-    t.gh = take(m);
+    t.items = c.take<HintAcc>(16 * m);
+    t.key_s = c.take<uint64_t>(8 * m);
+    t.val_in = c.take<uint32_t>(4 * m);
+    t.val_s = c.take<uint32_t>(4 * m);
+    t.val_r = c.take<uint32_t>(4 * m);
+    t.list = c.take<uint32_t>(4 * m);
+    t.fa = c.take<uint32_t>(4 * m);
+    t.fb = c.take<uint32_t>(4 * m);
+    t.fl = c.take(m);
+    t.gh = c.take(m);
     t.tmp_bytes = tmp_bytes;
-    t.tmp = take(t.tmp_bytes);
+    t.tmp = c.take(t.tmp_bytes);
     if (w) *w = t;
-    return o;
+    return c.bytes();
 }
-
-inline uint32_t hint_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 2048); }
 
 inline int launch_hint_plan(const HintIn &in, const uint32_t *result, const uint64_t *keyhash, uint32_t first,
                             uint32_t split_cap, int64_t index_interval, uint32_t max_offset_in, uint32_t *item_rec,
@@ -564,7 +555,7 @@ inline int launch_hint_plan(const HintIn &in, const uint32_t *result, const uint
     HintWs w;
     hint_ws_layout(in.cap, (uint8_t *)ws, &w);
     const uint32_t M = in.cap - first;
-    const dim3 G(hint_grid(M + 1)), B(256);
+    const dim3 G(grid_for((uint64_t)M + 1, 256, 2048)), B(256);
     hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(HintCounters), s);
     if (e != hipSuccess) return (int)e;
     size_t tb;
@@ -621,7 +612,7 @@ inline int launch_hint_plan(const HintIn &in, const uint32_t *result, const uint
 inline int launch_hint_write(const HintFile &f, uint8_t *out, uint64_t out_cap, uint32_t *totals, hipStream_t s) {
     // 16 + 289 (n - first) bytes at the most: 23 + 250 of an item and 16 of its index entry
     const uint64_t chunks = ((uint64_t)kHintHead + 289ull * f.in.cap + 15) / 16;
-    hipLaunchKernelGGL(k_hint_file, dim3(hint_grid(chunks)), dim3(256), 0, s, f, f.in.cap, out, out_cap, totals);
+    hipLaunchKernelGGL(k_hint_file, dim3(grid_for(chunks, 256, 2048)), dim3(256), 0, s, f, f.in.cap, out, out_cap, totals);
     return (int)hipGetLastError();
 }
 

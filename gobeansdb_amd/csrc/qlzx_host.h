@@ -3,7 +3,8 @@
 // (the batch launcher's side streams, the single-call contexts) need at process exit.  Included by
 // the files that hold host drivers (qlzx_decode_batch.hip, qlzx_decode_huge.hip,
 // qlzx_encode_huge.hip, qlzx_service.hip, qlzx_single.hip, qlzx_api.hip); qlzx_k2.hip's unit has
-// no use for it.
+// no use for it.  What the record-file kernels and their launchers share (replay, read, write, gc,
+// hint) is qlzx_recfile.h's, not this file's.
 #pragma once
 
 #include <atomic>

@@ -7,14 +7,14 @@
 // Three steps around qlzx_decompress_batch, like the replay's:
 //   check   k_rd_check: per request the size checks in readRecordAt's order and the record CRC;
 //           records with a CRC span over kRpLong go through k_rp_crc_long (qlzx_replay.hip),
-//           listed by request index;
-//   plan    the requests that passed and carry FLAG_COMPRESS, compacted in request order with
-//           the replay's scan kernels, ScatterComp and k_rp_dstoff;
+//           listed by request index (LongList, qlzx_recfile.h);
+//   plan    the requests that passed and carry FLAG_COMPRESS, compacted in request order
+//           (launch_compact and k_rp_dstoff of qlzx_recfile.h, the replay's ScatterComp);
 //   finish  the replay's finish kernels under a validity predicate: failed requests get zeros.
 // The CRC is checked BEFORE the plan, not fused into the decoder: it is readRecordAt's order, and
 // the QuickLZ header of a body that fails its CRC (it can claim up to BodyMax) must never size
 // the output buffer or route the batch to the whole-GPU decoder.
-#include "qlzx_device.h"
+#include "qlzx_recfile.h"
 
 namespace qlzx {
 
@@ -26,7 +26,7 @@ struct RdCounters {
 // CRC tables in LDS once per workgroup, a grid-stride loop over 64-request groups).  One header
 // load per lane classifies them; the survivors are CRCed one at a time by the whole wave
 // (wave_crc: any alignment and length).  The first failing check of readRecordAt's order is the
-// verdict:
+// verdict (rec_pos_verdict, then rec_size_verdict, then the CRC):
 //   rec_off % 256 != 0                QLZX_RD_ALIGN       positions are in units of 256, store/leaf.go:56-65
 //   rec_off + 24 > size               QLZX_RD_EOF_HEADER  store/datafile.go:123
 //   ksz == 0 || ksz > max_key         QLZX_RD_KEY_SIZE    :129, config/mc_config.go:33-35
@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(256) k_rd_check(const uint8_t *data, uint64_t 
                                                   uint32_t max_key, uint64_t body_max, const uint8_t *want_key,
                                                   const uint64_t *want_key_off, const uint32_t *want_key_len,
                                                   int32_t *rd_status, uint8_t *key_eq, int32_t *hdr, RdCounters *cnt,
-                                                  uint32_t *lng, uint32_t *lacc, uint32_t *ldone) {
+                                                  LongList ll) {
     __shared__ uint32_t tab[kCrcLdsWords];
     load_crc_lds(tab);
     __syncthreads();
@@ -54,17 +54,14 @@ __global__ void __launch_bounds__(256) k_rd_check(const uint8_t *data, uint64_t 
         int32_t st = QLZX_RD_ALIGN;
         uint32_t h[6] = {0, 0, 0, 0, 0, 0};
         if (in) {
-            if (off % kRpSlot != 0) st = QLZX_RD_ALIGN;
-            else if (off > size || size - off < kRpHdr) st = QLZX_RD_EOF_HEADER;
-            else {
+            RecVerdict v = rec_pos_verdict(off, size);
+            if (v == kRecOk) {
                 const uint2 *q = (const uint2 *)(data + off);  // records are 256-B aligned
                 const uint2 a = q[0], b = q[1], c = q[2];
                 h[0] = a.x, h[1] = a.y, h[2] = b.x, h[3] = b.y, h[4] = c.x, h[5] = c.y;
-                if (h[4] == 0 || h[4] > max_key) st = QLZX_RD_KEY_SIZE;
-                else if ((uint64_t)h[5] > body_max) st = QLZX_RD_VALUE_SIZE;
-                else if (size - off - kRpHdr < (uint64_t)h[4] + h[5]) st = QLZX_RD_EOF_BODY;
-                else st = QLZX_RD_OK;  // so far: the CRC decides
+                v = rec_size_verdict(h[4], h[5], size - off - kRpHdr, max_key, body_max);
             }
+            st = v;  // QLZX_RD_OK so far: the CRC decides
 #pragma unroll
             for (int k = 0; k < 6; k++) hdr[6 * (uint64_t)i + k] = (int32_t)h[k];
             if (st != QLZX_RD_OK) {
@@ -89,10 +86,7 @@ __global__ void __launch_bounds__(256) k_rd_check(const uint8_t *data, uint64_t 
             const uint32_t len = 20 + ksz + vsz;  // header[4:24] ‖ key ‖ value
             if (len > kRpLong) {
                 if (lane == 0) {
-                    const uint32_t j = atomicAdd(&cnt->nlong, 1u);
-                    lng[j] = ic;
-                    lacc[j] = 0;
-                    ldone[j] = 0;
+                    ll.push(ic);
                     if (key_eq) key_eq[ic] = (uint8_t)keq;
                 }
                 continue;
@@ -143,20 +137,15 @@ struct RdWs {
     uint32_t *lng, *lacc, *ldone, *tiles;
 };
 inline size_t read_ws_layout(uint32_t n, uint8_t *base, RdWs *w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t *p = base ? base + o : nullptr;
-        o += rp_align(bytes);
-        return p;
-    };
+    WsCarver c{base};
     RdWs t;
-    t.cnt = (RdCounters *)take(sizeof(RdCounters));
-    t.lng = (uint32_t *)take(4 * (size_t)n);
-    t.lacc = (uint32_t *)take(4 * (size_t)n);
-    t.ldone = (uint32_t *)take(4 * (size_t)n);
-    t.tiles = (uint32_t *)take(4 * ((size_t)n / kScanTile + 2));
+    t.cnt = c.take<RdCounters>(sizeof(RdCounters));
+    t.lng = c.take<uint32_t>(4 * (size_t)n);
+    t.lacc = c.take<uint32_t>(4 * (size_t)n);
+    t.ldone = c.take<uint32_t>(4 * (size_t)n);
+    t.tiles = c.take<uint32_t>(4 * ((size_t)n / kScanTile + 2));
     if (w) *w = t;
-    return o;
+    return c.bytes();
 }
 
 inline int launch_read_plan(const uint8_t *data, uint64_t size, const uint64_t *rec_off, uint32_t n, uint32_t max_key,
@@ -169,19 +158,14 @@ inline int launch_read_plan(const uint8_t *data, uint64_t size, const uint64_t *
     read_ws_layout(n, (uint8_t *)ws, &w);
     hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(RdCounters), s);
     if (e != hipSuccess) return (int)e;
-    const uint32_t ngroups = (n + 63) / 64;
-    const uint32_t grid = std::min<uint32_t>((ngroups + 3) / 4, 2048);
-    hipLaunchKernelGGL(k_rd_check, dim3(grid), dim3(256), 0, s, data, size, rec_off, n, max_key, body_max, want_key,
-                       want_key_off, want_key_len, rd_status, key_eq, hdr, w.cnt, w.lng, w.lacc, w.ldone);
-    hipLaunchKernelGGL(k_rp_crc_long<RdLongReqs>, dim3(2048), dim3(256), 0, s, data, (const uint32_t *)&w.cnt->nlong,
-                       RdLongReqs{rec_off, rd_status, key_eq, &w.cnt->nok}, (const uint32_t *)w.lng, w.lacc, w.ldone);
+    const LongList ll{&w.cnt->nlong, w.lng, w.lacc, w.ldone};
+    hipLaunchKernelGGL(k_rd_check, dim3(grid_for((n + 63) / 64, 4, 2048)), dim3(256), 0, s, data, size, rec_off, n,
+                       max_key, body_max, want_key, want_key_off, want_key_len, rd_status, key_eq, hdr, w.cnt, ll);
+    hipLaunchKernelGGL(k_rp_crc_long<RdLongReqs>, dim3(2048), dim3(256), 0, s, data,
+                       RdLongReqs{rec_off, rd_status, key_eq, &w.cnt->nok}, ll);
     // the compressed survivors in request order, then their destination offsets and the totals
-    const uint32_t ntiles = (n + kScanTile - 1) / kScanTile;
-    RdCompFlag cf{rd_status, hdr};
-    hipLaunchKernelGGL(k_scan_tiles<RdCompFlag>, dim3(ntiles), dim3(256), 0, s, cf, n, w.tiles);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, w.tiles, ntiles, &w.cnt->ncomp);
-    hipLaunchKernelGGL((k_scan_apply<RdCompFlag, ScatterComp>), dim3(ntiles), dim3(256), 0, s, cf,
-                       ScatterComp{data, rec_off, comp_idx, comp_len, comp_dsize, comp_off}, n, w.tiles);
+    launch_compact(RdCompFlag{rd_status, hdr}, ScatterComp{data, rec_off, comp_idx, comp_len, comp_dsize, comp_off}, n,
+                   w.tiles, &w.cnt->ncomp, s);
     hipLaunchKernelGGL(k_rp_dstoff, dim3(1), dim3(1024), 0, s, (const uint32_t *)comp_dsize,
                        (const uint32_t *)&w.cnt->ncomp, comp_dst_off, totals, (const uint32_t *)&w.cnt->nok);
     return (int)hipGetLastError();
@@ -196,7 +180,7 @@ inline int launch_read_finish(const uint8_t *data, const uint64_t *rec_off, uint
     static_assert(QLZX_OK == 0, "dec_status is cleared with a memset");
     const hipError_t e = hipMemsetAsync(dec_status, 0, (size_t)n * sizeof(int32_t), s);
     if (e != hipSuccess) return (int)e;
-    const uint32_t grid = std::min<uint32_t>((n + 255) / 256, 4096);
+    const uint32_t grid = grid_for(n);
     const RdOkRequests ok{n, rd_status};
     hipLaunchKernelGGL(k_rp_finish_vals<RdOkRequests>, dim3(grid), dim3(256), 0, s, data, rec_off, ok, flag, value_len,
                        in_out, val_off);

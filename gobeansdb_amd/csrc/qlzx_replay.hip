@@ -19,31 +19,22 @@
 //   4. the path from the start position is marked by pointer doubling
 //      (log2 rounds) and compacted into the visited record list with each
 //      record's sizeBroken.
-#include "qlzx_device.h"
+#include "qlzx_recfile.h"
 
 namespace qlzx {
 
-constexpr uint32_t kRpSlot = 256;
-constexpr uint32_t kRpHdr = 24;
 enum : uint8_t { kSlotBadSize = 1, kSlotTrunc = 2, kSlotPartial = 3, kSlotCand = 4 };
-constexpr uint32_t kScanTile = 1024;  // elements per scan tile (256 threads x 4)
 
 struct RpCounters {
     uint32_t ncand, m, r0, nvis, end_kind, nlong, pad[2];
 };
 
-// 1-2. slot classification (readRecordAt's size checks, store/datafile.go:128-136) and the
-// record CRC of every candidate, one wave each (wave_crc of qlzx_crc.h).  A wave
-// takes ~3 us per 4 KiB stripe, so a candidate longer than kRpLong (a false candidate can
-// claim up to BodyMax = 50 MiB) would be one wave's serial tail for the whole launch: those go
-// to a list (lng[], their per-list XOR accumulator and segment counter zeroed here) and are
-// cut into kRpSeg segments that k_rp_crc_long spreads over every wave of the chip.
-constexpr uint32_t kRpLong = 128u << 10;
-constexpr uint32_t kRpSeg = 16u << 10;
-
+// 1-2. slot classification (readRecordAt's size checks, rec_size_verdict) and the record CRC of
+// every candidate, one wave each (wave_crc of qlzx_crc.h).  Candidates with a CRC span over
+// kRpLong go to the long list, which k_rp_crc_long spreads over every wave of the chip.
 __device__ __forceinline__ void rp_crc_verdict(const uint8_t *h, uint32_t s, uint32_t ksz, uint32_t vsz,
                                                uint32_t reg, uint32_t *rsz) {
-    if ((reg ^ 0xffffffffu) == *(const uint32_t *)h) rsz[s] = ((kRpHdr + ksz + vsz + 255u) >> 8) << 8;
+    if ((reg ^ 0xffffffffu) == *(const uint32_t *)h) rsz[s] = (uint32_t)pad256(kRpHdr + ksz + vsz);
 }
 
 // k_rp_scan (round 5): a wave takes 64 consecutive slots (16 KiB of chunk) at a time, classifies
@@ -53,7 +44,7 @@ __device__ __forceinline__ void rp_crc_verdict(const uint8_t *h, uint32_t s, uin
 // 2.2 + 1.5 ms per 4000 MiB chunk.  Long candidates still go to the k_rp_crc_long list.
 __global__ void __launch_bounds__(256) k_rp_scan(const uint8_t *data, uint64_t size, uint32_t nslots, uint32_t max_key,
                                                  uint64_t body_max, uint8_t *kind, uint32_t *rsz, RpCounters *cnt,
-                                                 uint32_t *lng, uint32_t *lacc, uint32_t *ldone) {
+                                                 LongList ll) {
     __shared__ uint32_t tab[kCrcLdsWords];
     load_crc_lds(tab);
     __syncthreads();
@@ -66,12 +57,11 @@ __global__ void __launch_bounds__(256) k_rp_scan(const uint8_t *data, uint64_t s
         const uint64_t off = (uint64_t)s * kRpSlot;
         uint8_t k = kSlotPartial;
         uint32_t ksz = 0, vsz = 0;
-        if (in && off + kRpHdr <= size) {
+        if (in && rec_pos_verdict(off, size) == kRecOk) {
             const uint2 kv = *(const uint2 *)(data + off + 16);
             ksz = kv.x, vsz = kv.y;
-            if (ksz == 0 || ksz > max_key || (uint64_t)vsz > body_max) k = kSlotBadSize;
-            else if (off + kRpHdr + ksz + vsz > size) k = kSlotTrunc;
-            else k = kSlotCand;
+            const RecVerdict v = rec_size_verdict(ksz, vsz, size - off - kRpHdr, max_key, body_max);
+            k = v == kRecOk ? kSlotCand : v == kRecEofBody ? kSlotTrunc : kSlotBadSize;
         }
         if (in) {
             rsz[s] = 0;
@@ -87,12 +77,7 @@ __global__ void __launch_bounds__(256) k_rp_scan(const uint8_t *data, uint64_t s
             const uint32_t len = 20 + k2 + v2;  // header[4:24] ‖ key ‖ value
             const uint8_t *h = data + (uint64_t)sc * kRpSlot;
             if (len > kRpLong) {
-                if (lane == 0) {
-                    const uint32_t j = atomicAdd(&cnt->nlong, 1u);
-                    lng[j] = sc;
-                    lacc[j] = 0;
-                    ldone[j] = 0;
-                }
+                if (lane == 0) ll.push(sc);
                 continue;
             }
             const uint32_t reg = wave_crc(tab, h + 4, len, 0xffffffffu, lane);
@@ -105,8 +90,8 @@ __global__ void __launch_bounds__(256) k_rp_scan(const uint8_t *data, uint64_t s
 // long candidates: every wave walks the (normally empty or tiny) list 64 entries at a time
 // (one load per lane, a wave scan of the segment counts) and takes the segments g of the
 // global segment sequence with g = wave id (mod all waves).  A segment's raw CRC, shifted over
-// the bytes after it, is XORed into its candidate's accumulator, and the wave that completes
-// the last segment (counter == nseg) turns the sum into the verdict.
+// the bytes after it, goes into its candidate's accumulator (LongList::add), and the wave that
+// completes the last segment turns the sum into the verdict.  Nothing is stored but the verdict.
 // What a list entry names and where its verdict goes is the policy P's: rec(data, e) is the
 // entry's record, verdict(h, e, ksz, vsz, reg) takes the finished CRC register.  Replay lists
 // chunk slots (RpLongSlots); the batched read lists request indices (RdLongReqs, qlzx_read.hip).
@@ -118,10 +103,9 @@ struct RpLongSlots {
     }
 };
 template <class P>
-__global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const uint32_t *nlong, P pol,
-                                                     const uint32_t *lng, uint32_t *lacc, uint32_t *ldone) {
+__global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, P pol, LongList ll) {
     __shared__ uint32_t tab[kCrcLdsWords];
-    const uint32_t nl = *nlong;
+    const uint32_t nl = *ll.n;
     if (nl == 0) return;
     load_crc_lds(tab);
     __syncthreads();
@@ -132,7 +116,7 @@ __global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const 
         const uint32_t e = e0 + lane;
         uint32_t s = 0, len = 0;
         if (e < nl) {
-            s = lng[e];
+            s = ll.idx[e];
             const uint2 kv = *(const uint2 *)(pol.rec(data, s) + 16);
             len = 20 + kv.x + kv.y;
         }
@@ -152,21 +136,17 @@ __global__ void __launch_bounds__(256) k_rp_crc_long(const uint8_t *data, const 
             const uint8_t *h = pol.rec(data, sl_s);
             // segment 0 carries the initial state; each register is shifted over the rest
             const uint32_t raw = crc_shift(wave_crc(tab, h + 4 + o, sl, o ? 0u : 0xffffffffu, lane), sl_len - o - sl);
-            if (lane == 0) {
-                atomicXor(&lacc[e0 + L], raw);
-                __threadfence();
-                if (atomicAdd(&ldone[e0 + L], 1u) == nseg - 1) {
-                    __threadfence();
-                    const uint2 kv = *(const uint2 *)(h + 16);
-                    pol.verdict(h, sl_s, kv.x, kv.y, atomicOr(&lacc[e0 + L], 0u));
-                }
+            uint32_t sum = 0;
+            if (lane == 0 && ll.add(e0 + L, raw, nseg, &sum)) {
+                const uint2 kv = *(const uint2 *)(h + 16);
+                pol.verdict(h, sl_s, kv.x, kv.y, sum);
             }
         }
         base += total;
     }
 }
 
-// ---- exclusive scan of per-element 0/1 flags over [0, n), three kernels ----
+// ---- the flags and scatters of the two compactions (launch_compact) ----
 struct ValidFlag {  // slot s is a valid record start
     const uint32_t *rsz;
     __device__ uint32_t operator()(uint32_t i) const { return rsz[i] != 0; }
@@ -176,79 +156,6 @@ struct VisitFlag {  // valid index i < m lies on the reader's path (m, m+1 are t
     const RpCounters *cnt;
     __device__ uint32_t operator()(uint32_t i) const { return i < cnt->m ? flag[i] : 0u; }
 };
-
-template <class F>
-__global__ void __launch_bounds__(256) k_scan_tiles(F f, uint32_t n, uint32_t *tile_sum) {
-    __shared__ uint32_t part[4];
-    const uint32_t base = blockIdx.x * kScanTile;
-    uint32_t c = 0;
-    for (uint32_t j = threadIdx.x; j < kScanTile; j += 256)
-        if (base + j < n) c += f(base + j);
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-
-// single workgroup: exclusive scan of tile sums in place; *total = sum
-__global__ void __launch_bounds__(1024) k_scan_top(uint32_t *tile_sum, uint32_t ntiles, uint32_t *total) {
-    __shared__ uint32_t wsum[16];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (uint32_t base = 0; base < ntiles; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < ntiles ? tile_sum[i] : 0u;
-        uint32_t x = v;  // inclusive wave scan
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t acc = 0;
-            for (int j = 0; j < 16; j++) { const uint32_t t = wsum[j]; wsum[j] = acc; acc += t; }
-        }
-        __syncthreads();
-        const uint32_t excl = carry + wsum[w] + x - v;
-        if (i < ntiles) tile_sum[i] = excl;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = excl + v;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-// per tile: local exclusive ranks + the tile's offset; g(i, idx, flag) scatters
-template <class F, class G>
-__global__ void __launch_bounds__(256) k_scan_apply(F f, G g, uint32_t n, const uint32_t *tile_sum) {
-    __shared__ uint32_t wsum[4];
-    const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * 4;
-    uint32_t v[4], c = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        v[j] = (base + j < n) ? f(base + j) : 0u;
-        c += v[j];
-    }
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x = c;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    uint32_t woff = 0;
-    for (uint32_t j = 0; j < w; j++) woff += wsum[j];
-    uint32_t idx = tile_sum[blockIdx.x] + woff + x - c;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        if (base + j < n) g(base + j, idx, v[j]);
-        idx += v[j];
-    }
-}
 
 struct ScatterValid {  // vidx[s] = #valid slots before s; A[vidx] = s for valid s
     uint32_t *vidx, *A;
@@ -324,30 +231,14 @@ __global__ void k_rp_finish(RpCounters *cnt, const uint8_t *flag, uint32_t *resu
     result[3] = m;
 }
 
-// ---- Getvhash (store/item.go:89-100) with the sign-extending Fnv1a (utils/hash.go:8-16) ----
-__device__ __forceinline__ uint32_t fnv1a_bytes(const uint8_t *p, uint32_t n, uint32_t h) {
-    for (uint32_t i = 0; i < n; i++) {
-        h ^= (uint32_t)(int32_t)(int8_t)p[i];
-        h *= 0x01000193u;
-    }
-    return h;
-}
-
+// ---- Getvhash (fnv1a_bytes of qlzx_recfile.h) of a list of values ----
 __global__ void __launch_bounds__(64) k_vhash(const uint8_t *src, const uint64_t *off, const uint32_t *len,
                                               uint32_t n, uint16_t *out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint8_t *v = src + off[i];
     const uint32_t l = len[i];
-    uint32_t h = l * 97u;
-    if (l <= 1024) {
-        h += fnv1a_bytes(v, l, 0x811c9dc5u);
-    } else {
-        h += fnv1a_bytes(v, 512, 0x811c9dc5u);
-        h *= 97u;
-        h += fnv1a_bytes(v + l - 512, 512, 0x811c9dc5u);
-    }
-    out[i] = (uint16_t)h;
+    out[i] = getvhash(v, l);
 }
 
 // ---- replay plan / finish (store/item.go:163-176 around the batch decoder, no host parse) ----
@@ -355,8 +246,6 @@ __global__ void __launch_bounds__(64) k_vhash(const uint8_t *src, const uint64_t
 // offset and length, its decompressed size (the QuickLZ header, quicklz.go:32-44; 0 when the body
 // is shorter than a header, which the decoder reports) and a 256-B-aligned destination offset in
 // one packed output buffer.  totals = {n, ncomp, max_dsize, out_bytes_lo, out_bytes_hi}.
-constexpr uint32_t kFlagCompress = 0x00010000u;
-constexpr uint32_t kBodyMax = 50u << 20;
 struct CompFlag {
     const uint8_t *data;
     const uint64_t *off;
@@ -396,61 +285,6 @@ __global__ void __launch_bounds__(256) k_rp_headers(const uint8_t *data, const u
         const uint32_t *h = (const uint32_t *)(data + off[j]);  // records are 256-B aligned
 #pragma unroll
         for (int k = 0; k < 6; k++) hdr[6 * j + k] = (int32_t)h[k];
-    }
-}
-// destination offsets: exclusive scan of the 256-B-rounded sizes (u64) by one workgroup.  Wave
-// w owns the contiguous range [w P, (w + 1) P) and walks it twice, 64 coalesced sizes per step
-// with the next step's load in flight: first its sum, then (after one scan of the 16 sums) the
-// offsets by a wave scan with a carry -- no workgroup barrier per step (round 4 synchronised
-// the workgroup four times per 1024 sizes: 265 us for 224 K records).
-__global__ void __launch_bounds__(1024) k_rp_dstoff(const uint32_t *comp_dsize, const uint32_t *ncomp_p,
-                                                     uint64_t *dst_off, uint32_t *totals, const uint32_t *result) {
-    __shared__ uint64_t wsum[16];
-    __shared__ uint32_t mx[16];
-    const uint32_t nc = *ncomp_p, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t per = ((nc + 15) / 16 + 63) & ~63u;
-    const uint32_t lo = w * per < nc ? w * per : nc, hi = lo + per < nc ? lo + per : nc;
-    auto rnd = [](uint32_t d) { return ((uint64_t)d + 255) & ~(uint64_t)255; };
-    uint64_t sum = 0;
-    uint32_t mymax = 0;
-    uint32_t nxt = lo + lane < hi ? comp_dsize[lo + lane] : 0u;
-    for (uint32_t i = lo; i < hi; i += 64) {
-        const uint32_t d = nxt;
-        nxt = i + 64 + lane < hi ? comp_dsize[i + 64 + lane] : 0u;
-        sum += rnd(d);
-        mymax = max(mymax, d);
-    }
-    for (int k = 32; k >= 1; k >>= 1) {
-        sum += __shfl_xor(sum, k, 64);
-        mymax = max(mymax, (uint32_t)__shfl_xor(mymax, k, 64));
-    }
-    if (lane == 0) wsum[w] = sum, mx[w] = mymax;
-    __syncthreads();
-    uint64_t carry = 0, total = 0;
-    for (uint32_t j = 0; j < 16; j++) {
-        carry += j < w ? wsum[j] : 0;
-        total += wsum[j];
-    }
-    nxt = lo + lane < hi ? comp_dsize[lo + lane] : 0u;
-    for (uint32_t i = lo; i < hi; i += 64) {
-        const uint64_t v = i + lane < hi ? rnd(nxt) : 0;
-        nxt = i + 64 + lane < hi ? comp_dsize[i + 64 + lane] : 0u;
-        uint64_t x = v;  // inclusive wave scan
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint64_t y = __shfl_up(x, k, 64);
-            if (lane >= (uint32_t)k) x += y;
-        }
-        if (i + lane < hi) dst_off[i + lane] = carry + x - v;
-        carry += __shfl(x, 63, 64);
-    }
-    if (threadIdx.x == 0) {
-        uint32_t m = 0;
-        for (int j = 0; j < 16; j++) m = max(m, mx[j]);
-        totals[0] = result[0];
-        totals[1] = nc;
-        totals[2] = m;
-        totals[3] = (uint32_t)total;
-        totals[4] = (uint32_t)(total >> 32);
     }
 }
 // After the batch decode of the compressed records: flag, value length, where the value lives
@@ -504,34 +338,52 @@ __global__ void __launch_bounds__(256) k_rp_vhash2(const uint8_t *data, const ui
         }
         const uint8_t *v = (in_out[j] ? outbuf : data) + val_off[j];
         const uint32_t l = (uint32_t)value_len[j];
-        uint32_t h = l * 97u;
-        if (l <= 1024) {
-            h += fnv1a_bytes(v, l, 0x811c9dc5u);
-        } else {
-            h += fnv1a_bytes(v, 512, 0x811c9dc5u);
-            h *= 97u;
-            h += fnv1a_bytes(v + l - 512, 512, 0x811c9dc5u);
-        }
-        vh[j] = (uint16_t)h;
+        vh[j] = getvhash(v, l);
     }
 }
 
-inline size_t replay_plan_ws_bytes(uint32_t cap) { return 256 + (((size_t)cap / kScanTile + 2) * 4 + 255) / 256 * 256; }
+// ---- workspace layouts ----
+inline size_t replay_plan_ws_layout(uint32_t cap, uint8_t *base, uint32_t **ncomp, uint32_t **tiles) {
+    WsCarver c{base};
+    uint32_t *n = c.take<uint32_t>(4), *t = c.take<uint32_t>(4 * ((size_t)cap / kScanTile + 2));
+    if (ncomp) *ncomp = n, *tiles = t;
+    return c.bytes();
+}
+struct RpWs {
+    RpCounters *cnt;
+    uint8_t *kind, *flag;
+    uint32_t *rsz, *vidx, *A, *J, *J2, *vis, *tiles;
+};
+inline size_t replay_ws_layout(uint64_t size, uint8_t *base, RpWs *w) {
+    const uint64_t ns = (size + kRpSlot - 1) / kRpSlot;
+    const size_t n = (size_t)ns + 2;
+    const size_t ntiles = (n + kScanTile - 1) / kScanTile;
+    WsCarver c{base};
+    RpWs t;
+    t.cnt = c.take<RpCounters>(sizeof(RpCounters));
+    t.kind = c.take(n);
+    t.flag = c.take(n);
+    t.rsz = c.take<uint32_t>(4 * n);
+    t.vidx = c.take<uint32_t>(4 * n);
+    t.A = c.take<uint32_t>(4 * n);
+    t.J = c.take<uint32_t>(4 * n);
+    t.J2 = c.take<uint32_t>(4 * n);
+    t.vis = c.take<uint32_t>(4 * n);
+    t.tiles = c.take<uint32_t>(4 * (ntiles + 1));
+    if (w) *w = t;
+    return c.bytes();
+}
 
 inline int launch_replay_plan(const uint8_t *data, const uint64_t *off, const uint32_t *result, uint32_t cap,
                               int32_t *hdr, uint32_t *comp_idx, uint64_t *comp_off, uint32_t *comp_len,
                               uint32_t *comp_dsize, uint64_t *comp_dst_off, uint32_t *totals, void *ws,
                               hipStream_t s) {
-    uint32_t *ncomp = (uint32_t *)ws, *tiles = (uint32_t *)((uint8_t *)ws + 256);
-    const uint32_t ntiles = (cap + kScanTile - 1) / kScanTile;
-    const uint32_t grid = std::min<uint32_t>((cap + 255) / 256, 4096);
     if (cap == 0) return (int)hipMemsetAsync(totals, 0, 5 * sizeof(uint32_t), s);
-    hipLaunchKernelGGL(k_rp_headers, dim3(grid), dim3(256), 0, s, data, off, result, hdr);
-    CompFlag cf{data, off, result};
-    hipLaunchKernelGGL(k_scan_tiles<CompFlag>, dim3(ntiles), dim3(256), 0, s, cf, cap, tiles);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, tiles, ntiles, ncomp);
-    hipLaunchKernelGGL((k_scan_apply<CompFlag, ScatterComp>), dim3(ntiles), dim3(256), 0, s, cf,
-                       ScatterComp{data, off, comp_idx, comp_len, comp_dsize, comp_off}, cap, tiles);
+    uint32_t *ncomp, *tiles;
+    replay_plan_ws_layout(cap, (uint8_t *)ws, &ncomp, &tiles);
+    hipLaunchKernelGGL(k_rp_headers, dim3(grid_for(cap)), dim3(256), 0, s, data, off, result, hdr);
+    launch_compact(CompFlag{data, off, result}, ScatterComp{data, off, comp_idx, comp_len, comp_dsize, comp_off}, cap,
+                   tiles, ncomp, s);
     hipLaunchKernelGGL(k_rp_dstoff, dim3(1), dim3(1024), 0, s, (const uint32_t *)comp_dsize, (const uint32_t *)ncomp,
                        comp_dst_off, totals, result);
     return (int)hipGetLastError();
@@ -543,7 +395,7 @@ inline int launch_replay_finish(const uint8_t *data, const uint64_t *off, const 
                                 uint32_t cap, int32_t *flag, int32_t *value_len, uint8_t *in_out, uint64_t *val_off,
                                 uint16_t *vh, hipStream_t s) {
     if (cap == 0) return 0;
-    const uint32_t grid = std::min<uint32_t>((cap + 255) / 256, 4096);
+    const uint32_t grid = grid_for(cap);
     hipLaunchKernelGGL(k_rp_finish_vals<RpAllRecords>, dim3(grid), dim3(256), 0, s, data, off, RpAllRecords{result},
                        flag, value_len, in_out, val_off);
     hipLaunchKernelGGL(k_rp_finish_comp, dim3(grid), dim3(256), 0, s, totals + 1, comp_idx, cstatus, cdsize, cdst_off,
@@ -553,40 +405,6 @@ inline int launch_replay_finish(const uint8_t *data, const uint64_t *off, const 
     return (int)hipGetLastError();
 }
 
-// ---- workspace layout ----
-struct RpWs {
-    RpCounters *cnt;
-    uint8_t *kind, *flag;
-    uint32_t *rsz, *vidx, *A, *J, *J2, *vis, *tiles;
-};
-
-inline size_t rp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-inline size_t replay_ws_layout(uint64_t size, uint8_t *base, RpWs *w) {
-    const uint64_t ns = (size + kRpSlot - 1) / kRpSlot;
-    const size_t n = (size_t)ns + 2;
-    const size_t ntiles = (n + kScanTile - 1) / kScanTile;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t *p = base ? base + o : nullptr;
-        o += rp_align(bytes);
-        return p;
-    };
-    RpWs t;
-    t.cnt = (RpCounters *)take(sizeof(RpCounters));
-    t.kind = take(n);
-    t.flag = take(n);
-    t.rsz = (uint32_t *)take(4 * n);
-    t.vidx = (uint32_t *)take(4 * n);
-    t.A = (uint32_t *)take(4 * n);
-    t.J = (uint32_t *)take(4 * n);
-    t.J2 = (uint32_t *)take(4 * n);
-    t.vis = (uint32_t *)take(4 * n);
-    t.tiles = (uint32_t *)take(4 * (ntiles + 1));
-    if (w) *w = t;
-    return o;
-}
-
 inline int launch_replay_index(const uint8_t *data, uint64_t size, uint64_t start, uint32_t max_key,
                                uint64_t body_max, uint64_t *rec_off, uint32_t *rec_broken, uint32_t *result,
                                void *ws, hipStream_t s) {
@@ -594,26 +412,19 @@ inline int launch_replay_index(const uint8_t *data, uint64_t size, uint64_t star
     replay_ws_layout(size, (uint8_t *)ws, &w);
     const uint32_t nslots = (uint32_t)((size + kRpSlot - 1) / kRpSlot);
     const uint32_t n2 = nslots + 2;
-    const uint32_t ntiles = (n2 + kScanTile - 1) / kScanTile;
     const uint32_t g256 = (n2 + 255) / 256;
     hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(RpCounters), s);
     if (e != hipSuccess) return (int)e;
     // slot classification + candidate CRCs in one pass: a grid-stride loop over 64-slot groups,
     // one table load per workgroup, 8 workgroups per CU; the long-candidate list and its
     // accumulators borrow vis, J and J2 (written later)
-    const uint32_t ngroups = (nslots + 63) / 64;
-    const uint32_t scan_grid = (ngroups + 3) / 4 < 2048 ? (ngroups + 3) / 4 : 2048;
+    const LongList ll{&w.cnt->nlong, w.vis, w.J, w.J2};
     if (nslots)
-        hipLaunchKernelGGL(k_rp_scan, dim3(scan_grid), dim3(256), 0, s, data, size, nslots, max_key, body_max, w.kind,
-                           w.rsz, w.cnt, w.vis, w.J, w.J2);
-    hipLaunchKernelGGL(k_rp_crc_long<RpLongSlots>, dim3(2048), dim3(256), 0, s, data,
-                       (const uint32_t *)&w.cnt->nlong, RpLongSlots{w.rsz}, (const uint32_t *)w.vis, w.J, w.J2);
+        hipLaunchKernelGGL(k_rp_scan, dim3(grid_for((nslots + 63) / 64, 4, 2048)), dim3(256), 0, s, data, size, nslots,
+                           max_key, body_max, w.kind, w.rsz, w.cnt, ll);
+    hipLaunchKernelGGL(k_rp_crc_long<RpLongSlots>, dim3(2048), dim3(256), 0, s, data, RpLongSlots{w.rsz}, ll);
     // valid slots in order: vidx (exclusive count) and A
-    ValidFlag vf{w.rsz};
-    hipLaunchKernelGGL(k_scan_tiles<ValidFlag>, dim3(ntiles), dim3(256), 0, s, vf, nslots, w.tiles);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, w.tiles, ntiles, &w.cnt->m);
-    hipLaunchKernelGGL((k_scan_apply<ValidFlag, ScatterValid>), dim3(ntiles), dim3(256), 0, s, vf,
-                       ScatterValid{w.vidx, w.A}, nslots, w.tiles);
+    launch_compact(ValidFlag{w.rsz}, ScatterValid{w.vidx, w.A}, nslots, w.tiles, &w.cnt->m, s);
     // successors, start, and the path by pointer doubling
     hipLaunchKernelGGL(k_rp_next, dim3(g256), dim3(256), 0, s, size, nslots, start, w.kind, w.rsz, w.vidx, w.A,
                        w.cnt, w.J, w.flag);
@@ -624,11 +435,7 @@ inline int launch_replay_index(const uint8_t *data, uint64_t size, uint64_t star
         uint32_t *t = J; J = J2; J2 = t;
     }
     // visited records in order
-    VisitFlag ff{w.flag, w.cnt};
-    hipLaunchKernelGGL(k_scan_tiles<VisitFlag>, dim3(ntiles), dim3(256), 0, s, ff, nslots, w.tiles);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, w.tiles, ntiles, &w.cnt->nvis);
-    hipLaunchKernelGGL((k_scan_apply<VisitFlag, ScatterVisit>), dim3(ntiles), dim3(256), 0, s, ff,
-                       ScatterVisit{w.A, w.vis}, nslots, w.tiles);
+    launch_compact(VisitFlag{w.flag, w.cnt}, ScatterVisit{w.A, w.vis}, nslots, w.tiles, &w.cnt->nvis, s);
     hipLaunchKernelGGL(k_rp_emit, dim3((nslots + 255) / 256 + 1), dim3(256), 0, s, w.vis, w.cnt, w.rsz, start,
                        rec_off, rec_broken);
     hipLaunchKernelGGL(k_rp_finish, dim3(1), dim3(1), 0, s, w.cnt, w.flag, result);

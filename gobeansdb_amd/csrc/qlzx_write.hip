@@ -6,7 +6,7 @@
 // Three steps around two qlzx_compress_batch calls:
 //   plan    k_wr_plan: per record the size limits qlzx_read_plan enforces and TryCompress's
 //           candidate test with http.DetectContentType's audio/video rows on the value's first
-//           bytes; the candidates compacted in record order (the replay's scan kernels) into the
+//           bytes; the candidates compacted in record order (launch_compact) into the
 //           trial list, each destination len + 400 apart (k_rp_dstoff);
 //   decide  k_wr_decide: float32(csize) / float32(try_len) <= 0.7 per trial; the kept ones longer
 //           than the trial, compacted into the full-recompress list;
@@ -14,8 +14,8 @@
 //           wave per record writes header, key, value, CRC word and padding; a plain value's CRC
 //           is computed in the pass that copies it, a compressed value's comes from the compressor
 //           (fused, state 0) and is combined with the prefix's; records with a CRC span over
-//           kRpLong are cut into kRpSeg segments over the chip (k_wr_long).
-#include "qlzx_device.h"
+//           kRpLong are cut into kRpSeg segments over the chip (k_rec_long<WrLong>).
+#include "qlzx_recfile.h"
 
 namespace qlzx {
 
@@ -28,8 +28,6 @@ struct WrCounters {
     unsigned long long bound, bytes;
     uint32_t t5[10];  // k_rp_dstoff's totals; pads the struct to a multiple of 16 bytes
 };
-
-__host__ __device__ __forceinline__ uint64_t wr_pad256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 
 // The row of http.DetectContentType's audio/video table (Go 1.13 net/http/sniff.go, in table
 // order: audio/basic, audio/aiff, audio/mpeg, application/ogg, audio/midi, video/avi, audio/wave)
@@ -70,17 +68,14 @@ __global__ void __launch_bounds__(256) k_wr_plan(const uint8_t *values, const ui
         if (st == QLZX_WR_OK) {
             const uint64_t plain = (uint64_t)kRpHdr + ksz + vlen;
             nok++;
-            bound += wr_pad256(plain + 9);
-            c = ver[i] >= 0 && (flag[i] & (kFlagClientCompress | kFlagCompress)) == 0 && wr_pad256(plain) > kRpSlot;
+            bound += pad256(plain + 9);
+            c = ver[i] >= 0 && (flag[i] & (kFlagClientCompress | kFlagCompress)) == 0 && pad256(plain) > kRpSlot;
             if (c) c = ((not_compress >> wr_sniff(values + val_off[i], vlen)) & 1u) == 0;
         }
         wr_status[i] = st;
         cand[i] = c;
     }
-    for (int m = 32; m >= 1; m >>= 1) {
-        nok += __shfl_xor(nok, m, 64);
-        bound += __shfl_xor(bound, m, 64);
-    }
+    nok = wave_sum(nok), bound = wave_sum(bound);
     if ((threadIdx.x & 63) == 0 && nok) {
         atomicAdd(&cnt->nok, nok);
         atomicAdd(&cnt->bound, bound);
@@ -126,7 +121,7 @@ __global__ void __launch_bounds__(256) k_wr_decide(const uint32_t *totals, const
         keep[k] = kp;
         nkeep += kp;
     }
-    for (int m = 32; m >= 1; m >>= 1) nkeep += __shfl_xor(nkeep, m, 64);
+    nkeep = wave_sum(nkeep);
     if ((threadIdx.x & 63) == 0 && nkeep) atomicAdd(&cnt->nkeep, nkeep);
 }
 struct WrFullFlag {  // a kept trial that saw only the first 10 KiB: recompress the whole value
@@ -286,17 +281,13 @@ __device__ uint32_t wr_span(const uint32_t *lds, const WrRec &R, uint8_t *rec, u
             for (int k = 0; k < 4; k++) {
                 const int64_t xc = p + 16 * k;
                 if (xc < (int64_t)r0) continue;
-                uint32_t *d = (uint32_t *)(rec + xc);
-                if (xc == 0) d[1] = w[4 * k + 1], d[2] = w[4 * k + 2], d[3] = w[4 * k + 3];  // the CRC word comes last
-                else *(uint4 *)d = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+                store_rec_chunk(rec + xc, make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]), xc == 0);
             }
         }
 #pragma unroll
         for (int k = 0; k < 16; k += 2) c = crc_slice8(t8, c, cw[k], cw[k + 1]);
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) c = crc_mul_tab(mul + k * 1024, c) ^ __shfl_xor(c, 1 << k, 64);
-    return __shfl(c, 0, 64);
+    return crc_lane_merge(mul, c);
 }
 
 // The record's last bytes: reg continued over image[e16, end) (fewer than 16 bytes), and the
@@ -336,11 +327,14 @@ struct WrIn {
 
 // k_wr_assemble: a wave per record, grid-stride.  Failed records get zeros; a record that would
 // end past out_cap gets QLZX_WR_NO_SPACE and writes nothing; one whose CRC span exceeds kRpLong
-// goes to the k_wr_long list.
+// goes to the long list (k_rec_long<WrLong>).
 __global__ void __launch_bounds__(256) k_wr_assemble(WrIn in, uint32_t n, uint8_t *out, uint64_t out_cap,
                                                      int32_t *wr_status, uint64_t *rec_off, uint32_t *flag_out,
                                                      uint32_t *vsz, uint32_t *crc, WrCounters *cnt, uint32_t *lng,
                                                      uint32_t *lacc, uint32_t *ldone) {
+    // the list's arrays one by one, its counter taken from cnt: the kernel sits at the SGPR limit,
+    // and a fourth pointer argument costs a VGPR
+    const LongList ll{&cnt->nlong, lng, lacc, ldone};
     __shared__ uint32_t tab[kCrcLdsWords];
     load_crc_lds(tab);
     __syncthreads();
@@ -351,7 +345,7 @@ __global__ void __launch_bounds__(256) k_wr_assemble(WrIn in, uint32_t n, uint8_
         const uint64_t ro = rec_off[i];
         bool ok = wr_status[i] == QLZX_WR_OK;
         const WrRec R = in.rec(i);
-        const uint64_t rsz = wr_pad256(R.end);
+        const uint64_t rsz = pad256(R.end);
         if (ok && (ro > out_cap || out_cap - ro < rsz)) {
             ok = false;
             if (lane == 0) wr_status[i] = QLZX_WR_NO_SPACE;
@@ -363,12 +357,7 @@ __global__ void __launch_bounds__(256) k_wr_assemble(WrIn in, uint32_t n, uint8_
         nwritten++;
         bytes += rsz;
         if (R.end - 4 > kRpLong) {
-            if (lane == 0) {
-                const uint32_t j = atomicAdd(&cnt->nlong, 1u);
-                lng[j] = i;
-                lacc[j] = 0;
-                ldone[j] = 0;
-            }
+            if (lane == 0) ll.push(i);
             continue;
         }
         uint8_t *rec = out + ro;
@@ -387,49 +376,29 @@ __global__ void __launch_bounds__(256) k_wr_assemble(WrIn in, uint32_t n, uint8_
     }
 }
 
-// long records: as k_rp_crc_long, every wave takes the segments g of the global segment sequence
-// with g = wave id (mod all waves).  Segment r of a record is its image [r kRpSeg, (r + 1) kRpSeg)
-// (the last one runs to the record's end and writes the tail and the padding); its raw CRC,
-// shifted over the bytes after it, is XORed into the record's accumulator, and the wave that
-// completes the last segment writes the CRC word.
-__global__ void __launch_bounds__(256) k_wr_long(WrIn in, uint8_t *out, uint32_t *crc, const WrCounters *cnt,
-                                                 const uint32_t *lng, uint32_t *lacc, uint32_t *ldone) {
-    __shared__ uint32_t tab[kCrcLdsWords];
-    const uint32_t nl = cnt->nlong;
-    if (nl == 0) return;
-    load_crc_lds(tab);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wid = blockIdx.x * 4 + threadIdx.x / 64, nw = gridDim.x * 4;
-    uint64_t g = 0;
-    for (uint32_t e = 0; e < nl; e++) {
-        const uint32_t i = lng[e];
-        const WrRec R = in.rec(i);
-        uint8_t *rec = out + in.rec_off[i];
-        const uint32_t e16 = R.end & ~15u;
-        const uint32_t nseg = (e16 + kRpSeg - 1) / kRpSeg;
-        for (uint32_t r = (uint32_t)((wid + nw - g % nw) % nw); r < nseg; r += nw) {
-            const uint32_t r0 = r * kRpSeg;
-            const bool last = r == nseg - 1;
-            const uint32_t r1 = last ? e16 : r0 + kRpSeg;
-            uint32_t reg = wr_span(tab, R, rec, r0, r1, lane);
-            if (last) reg = wr_tail(tab, R, rec, e16, (uint32_t)wr_pad256(R.end), reg, lane);
-            else reg = crc_shift(reg, R.end - r1);
-            if (lane == 0) {
-                atomicXor(&lacc[e], reg);
-                __threadfence();
-                if (atomicAdd(&ldone[e], 1u) == nseg - 1) {
-                    __threadfence();
-                    uint32_t sum = atomicOr(&lacc[e], 0u);
-                    if (R.vzero) sum ^= in.vcrc[i];
-                    *(uint32_t *)rec = ~sum;
-                    crc[i] = ~sum;
-                }
-            }
-        }
-        g += nseg;
+// k_rec_long's policy: a long record's segments are spans of its image, the last one with the tail.
+struct WrLong {
+    WrIn in;
+    uint8_t *out;
+    uint32_t *crc;
+    struct Rec {
+        WrRec R;
+        uint8_t *dst;
+    };
+    __device__ Rec rec(uint32_t i) const { return Rec{in.rec(i), out + in.rec_off[i]}; }
+    __device__ bool valid(const Rec &) const { return true; }
+    __device__ uint32_t end(const Rec &r) const { return r.R.end; }
+    __device__ uint32_t segment(const uint32_t *lds, const Rec &r, uint32_t r0, uint32_t r1, bool last,
+                                uint32_t lane) const {
+        const uint32_t reg = wr_span(lds, r.R, r.dst, r0, r1, lane);
+        return last ? wr_tail(lds, r.R, r.dst, r1, (uint32_t)pad256(r.R.end), reg, lane) : reg;
     }
-}
+    __device__ void finish(uint32_t i, const Rec &r, uint32_t sum) const {
+        if (r.R.vzero) sum ^= in.vcrc[i];
+        *(uint32_t *)r.dst = ~sum;
+        crc[i] = ~sum;
+    }
+};
 
 // Getvhash of the ORIGINAL value (CalcValueHash runs before TryCompress in checkAndSet,
 // store/item.go:102); zeros for the records not written.
@@ -443,15 +412,7 @@ __global__ void __launch_bounds__(256) k_wr_vhash(const uint8_t *values, const u
         }
         const uint8_t *v = values + val_off[i];
         const uint32_t l = val_len[i];
-        uint32_t h = l * 97u;
-        if (l <= 1024) {
-            h += fnv1a_bytes(v, l, 0x811c9dc5u);
-        } else {
-            h += fnv1a_bytes(v, 512, 0x811c9dc5u);
-            h *= 97u;
-            h += fnv1a_bytes(v + l - 512, 512, 0x811c9dc5u);
-        }
-        vh[i] = (uint16_t)h;
+        vh[i] = getvhash(v, l);
     }
 }
 __global__ void k_wr_totals3(uint32_t *totals3, const WrCounters *cnt) {
@@ -468,29 +429,22 @@ struct WrWs {
     uint64_t *soff;
 };
 inline size_t write_ws_layout(uint32_t n, uint8_t *base, WrWs *w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t *p = base ? base + o : nullptr;
-        o += rp_align(bytes);
-        return p;
-    };
+    WsCarver c{base};
     WrWs t;
-    t.cnt = (WrCounters *)take(sizeof(WrCounters));
-    t.cand = take((size_t)n);
-    t.cap = (uint32_t *)take(4 * (size_t)n);
-    t.sz = (uint32_t *)take(4 * (size_t)n);
-    t.sel = (uint32_t *)take(4 * (size_t)n);
-    t.vcrc = (uint32_t *)take(4 * (size_t)n);
-    t.lng = (uint32_t *)take(4 * (size_t)n);
-    t.lacc = (uint32_t *)take(4 * (size_t)n);
-    t.ldone = (uint32_t *)take(4 * (size_t)n);
-    t.soff = (uint64_t *)take(8 * (size_t)n);
-    t.tiles = (uint32_t *)take(4 * ((size_t)n / kScanTile + 2));
+    t.cnt = c.take<WrCounters>(sizeof(WrCounters));
+    t.cand = c.take((size_t)n);
+    t.cap = c.take<uint32_t>(4 * (size_t)n);
+    t.sz = c.take<uint32_t>(4 * (size_t)n);
+    t.sel = c.take<uint32_t>(4 * (size_t)n);
+    t.vcrc = c.take<uint32_t>(4 * (size_t)n);
+    t.lng = c.take<uint32_t>(4 * (size_t)n);
+    t.lacc = c.take<uint32_t>(4 * (size_t)n);
+    t.ldone = c.take<uint32_t>(4 * (size_t)n);
+    t.soff = c.take<uint64_t>(8 * (size_t)n);
+    t.tiles = c.take<uint32_t>(4 * ((size_t)n / kScanTile + 2));
     if (w) *w = t;
-    return o;
+    return c.bytes();
 }
-
-inline uint32_t wr_grid(uint32_t n) { return std::min<uint32_t>((n + 255) / 256, 4096); }
 
 inline int launch_write_plan(const uint8_t *values, const uint64_t *val_off, const uint32_t *val_len,
                              const uint32_t *key_len, const uint32_t *flag, const int32_t *ver, uint32_t n,
@@ -502,14 +456,10 @@ inline int launch_write_plan(const uint8_t *values, const uint64_t *val_off, con
     write_ws_layout(n, (uint8_t *)ws, &w);
     const hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(WrCounters), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_wr_plan, dim3(wr_grid(n)), dim3(256), 0, s, values, val_off, val_len, key_len, flag, ver, n,
+    hipLaunchKernelGGL(k_wr_plan, dim3(grid_for(n)), dim3(256), 0, s, values, val_off, val_len, key_len, flag, ver, n,
                        max_key, body_max, not_compress, wr_status, w.cand, w.cnt);
-    const uint32_t ntiles = (n + kScanTile - 1) / kScanTile;
-    WrCandFlag cf{w.cand};
-    hipLaunchKernelGGL(k_scan_tiles<WrCandFlag>, dim3(ntiles), dim3(256), 0, s, cf, n, w.tiles);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, w.tiles, ntiles, &w.cnt->t5[0]);
-    hipLaunchKernelGGL((k_scan_apply<WrCandFlag, ScatterTry>), dim3(ntiles), dim3(256), 0, s, cf,
-                       ScatterTry{val_off, val_len, try_idx, try_len, w.cap, try_off}, n, w.tiles);
+    launch_compact(WrCandFlag{w.cand}, ScatterTry{val_off, val_len, try_idx, try_len, w.cap, try_off}, n, w.tiles,
+                   &w.cnt->t5[0], s);
     hipLaunchKernelGGL(k_rp_dstoff, dim3(1), dim3(1024), 0, s, (const uint32_t *)w.cap,
                        (const uint32_t *)&w.cnt->t5[0], try_dst_off, totals, (const uint32_t *)&w.cnt->nok);
     hipLaunchKernelGGL(k_wr_totals, dim3(1), dim3(1), 0, s, totals, (const WrCounters *)w.cnt, 1);
@@ -526,14 +476,11 @@ inline int launch_write_decide(const uint64_t *val_off, const uint32_t *val_len,
     write_ws_layout(n, (uint8_t *)ws, &w);
     const hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(WrCounters), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_wr_decide, dim3(wr_grid(n)), dim3(256), 0, s, totals, try_len, try_csize, try_status, keep,
+    hipLaunchKernelGGL(k_wr_decide, dim3(grid_for(n)), dim3(256), 0, s, totals, try_len, try_csize, try_status, keep,
                        w.cnt);
-    const uint32_t ntiles = (n + kScanTile - 1) / kScanTile;
-    WrFullFlag ff{totals, try_idx, try_len, val_len, keep};
-    hipLaunchKernelGGL(k_scan_tiles<WrFullFlag>, dim3(ntiles), dim3(256), 0, s, ff, n, w.tiles);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, s, w.tiles, ntiles, &w.cnt->t5[0]);
-    hipLaunchKernelGGL((k_scan_apply<WrFullFlag, ScatterFull>), dim3(ntiles), dim3(256), 0, s, ff,
-                       ScatterFull{try_idx, val_len, val_off, full_idx, full_len, w.cap, full_off}, n, w.tiles);
+    launch_compact(WrFullFlag{totals, try_idx, try_len, val_len, keep},
+                   ScatterFull{try_idx, val_len, val_off, full_idx, full_len, w.cap, full_off}, n, w.tiles,
+                   &w.cnt->t5[0], s);
     hipLaunchKernelGGL(k_rp_dstoff, dim3(1), dim3(1024), 0, s, (const uint32_t *)w.cap,
                        (const uint32_t *)&w.cnt->t5[0], full_dst_off, totals2, (const uint32_t *)&w.cnt->nkeep);
     hipLaunchKernelGGL(k_wr_totals, dim3(1), dim3(1), 0, s, totals2, (const WrCounters *)w.cnt, 0);
@@ -557,9 +504,9 @@ inline int launch_write_finish(const WrFinishArgs &a, uint32_t n, uint8_t *out, 
     write_ws_layout(n, (uint8_t *)ws, &w);
     const hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(WrCounters), s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_wr_sizes, dim3(wr_grid(n)), dim3(256), 0, s, a.val_off, a.val_len, a.key_len, a.flag,
+    hipLaunchKernelGGL(k_wr_sizes, dim3(grid_for(n)), dim3(256), 0, s, a.val_off, a.val_len, a.key_len, a.flag,
                        (const int32_t *)wr_status, n, flag_out, vsz, w.sz, w.sel, w.soff, w.cnt);
-    hipLaunchKernelGGL(k_wr_apply, dim3(wr_grid(n)), dim3(256), 0, s, a.totals, a.try_idx, a.try_len, a.try_dst_off,
+    hipLaunchKernelGGL(k_wr_apply, dim3(grid_for(n)), dim3(256), 0, s, a.totals, a.try_idx, a.try_len, a.try_dst_off,
                        a.try_csize, a.try_crc, a.keep, a.totals2, a.full_idx, a.full_dst_off, a.full_csize,
                        a.full_status, a.full_crc, a.val_len, a.key_len, flag_out, vsz, w.sz, w.sel, w.soff, w.vcrc);
     // record offsets: the exclusive scan of the padded sizes (0 for a failed record)
@@ -567,12 +514,12 @@ inline int launch_write_finish(const WrFinishArgs &a, uint32_t n, uint8_t *out, 
                        rec_off, &w.cnt->t5[0], (const uint32_t *)&w.cnt->zero);
     const WrIn in{a.values, a.keys,  a.trial_buf, a.full_buf, a.key_off, a.key_len, a.ts,
                   a.ver,    flag_out, vsz,         w.sel,      w.vcrc,    w.soff,    rec_off};
-    hipLaunchKernelGGL(k_wr_assemble, dim3(std::min<uint32_t>((n + 3) / 4, 2048)), dim3(256), 0, s, in, n, out,
-                       out_cap, wr_status, rec_off, flag_out, vsz, crc, w.cnt, w.lng, w.lacc, w.ldone);
-    hipLaunchKernelGGL(k_wr_long, dim3(2048), dim3(256), 0, s, in, out, crc, (const WrCounters *)w.cnt,
-                       (const uint32_t *)w.lng, w.lacc, w.ldone);
+    hipLaunchKernelGGL(k_wr_assemble, dim3(grid_for(n, 4, 2048)), dim3(256), 0, s, in, n, out, out_cap, wr_status,
+                       rec_off, flag_out, vsz, crc, w.cnt, w.lng, w.lacc, w.ldone);
+    hipLaunchKernelGGL(k_rec_long<WrLong>, dim3(2048), dim3(256), 0, s, WrLong{in, out, crc},
+                       LongList{&w.cnt->nlong, w.lng, w.lacc, w.ldone});
     if (vhash)
-        hipLaunchKernelGGL(k_wr_vhash, dim3(wr_grid(n)), dim3(256), 0, s, a.values, a.val_off, a.val_len,
+        hipLaunchKernelGGL(k_wr_vhash, dim3(grid_for(n)), dim3(256), 0, s, a.values, a.val_off, a.val_len,
                            (const int32_t *)wr_status, n, vhash);
     hipLaunchKernelGGL(k_wr_totals3, dim3(1), dim3(1), 0, s, totals3, (const WrCounters *)w.cnt);
     return (int)hipGetLastError();

@@ -136,10 +136,11 @@ def test_every_tail_length(cuda):
 @functools.lru_cache(maxsize=None)
 def _longs():
     """Values whose CRC span 20 + ksz + vsz is 131072 (the last wave-per-record size), 131073 and
-    well past it, between small records."""
+    well past it, then two segmented ones whose image end E = 24 + ksz + vsz leaves no tail bytes
+    (E % 16 == 0) and a last segment of a single 16-byte chunk, between small records."""
     rnd = random.Random(22)
     recs = []
-    for i, v in enumerate((131049, 131050, 200000)):
+    for i, v in enumerate((131049, 131050, 200000, 131109, 131066)):
         recs.append((b"s%02d" % i, rnd.randbytes(100 + i)))
         recs.append((b"L%02d" % i, rnd.randbytes(v)))
     recs.append((b"end", b"tail"))
@@ -151,12 +152,14 @@ def test_long_records(cuda):
     from gobeansdb_amd import gc, replay
     data = _longs()
     recs, _ = R.stream_all(data)
-    assert [20 + len(r.key) + len(r.body) for r in recs[1::2]] == [131072, 131073, 200023]
-    keep = [True, True, False, True, True, True, True]
+    assert [20 + len(r.key) + len(r.body) for r in recs[1::2]] == [131072, 131073, 200023, 131132, 131089]
+    ends = [24 + len(r.key) + len(r.body) for r in recs[7:10:2]]
+    assert ends[0] % 16 == 0 and (ends[1] & ~15) % (16 << 10) == 16
+    keep = [True, True, False, True, True, True, True, True, True, True, True]
     want_chunks, want_pos = G.gc_rewrite(data, keep, data_file_max=gc.DATA_FILE_MAX)
     d = _dev(data, cuda)
     off = replay.index(d)[0]
-    assert off.numel() == 7
+    assert off.numel() == 11
     out = _out(len(want_chunks[0]), cuda)
     res = gc.rewrite_batch(d, off, torch.tensor(keep, device=cuda), out=out)
     torch.cuda.synchronize()

@@ -261,11 +261,17 @@ def test_long_values(cuda, texts):
     big = O.gen_text(4, 9, 400000)
     assert len(_compress(big)) > (128 << 10)             # a compressed value on the segment path
     assert 28000 < len(_compress(texts[70000])) < 36000
-    keys = [b"img140", b"pre140", b"text70", b"text400", b"tail"]
-    vals = [img, img[::-1], texts[70000], big, b"x" * 40]
-    res, rows = _run(keys, vals, flags=[0, FC, 0, 0, 0], misalign=True, seed=2)
-    assert [r[3] for r in rows] == [0, FC, FC, FC, 0]
+    # client-compressed noise is copied as it is, so the image end E = 24 + ksz + vsz is exact: the
+    # last wave-per-record size, the first segmented one, no tail bytes, a last segment of one chunk
+    noise = np.random.default_rng(3).integers(0, 256, 132000, dtype=np.uint8).tobytes()
+    ends = [(128 << 10) + 4, (128 << 10) + 5, (128 << 10) + 64, 8 * (16 << 10) + 16 + 5]
+    assert ends[2] % 16 == 0 and (ends[3] & ~15) % (16 << 10) == 16
+    keys = [b"img140", b"pre140", b"text70", b"text400"] + [b"edge%d" % i for i in range(4)] + [b"tail"]
+    vals = [img, img[::-1], texts[70000], big] + [noise[i:i + e - 29] for i, e in enumerate(ends)] + [b"x" * 40]
+    res, rows = _run(keys, vals, flags=[0, FC, 0, 0, FCC, FCC, FCC, FCC, 0], misalign=True, seed=2)
+    assert [r[3] for r in rows] == [0, FC, FC, FC, FCC, FCC, FCC, FCC, 0]
     assert [r[4] for r in rows][:2] == [140000, 140000]
+    assert [24 + 5 + r[4] for r in rows[4:8]] == ends
 
 
 def test_stored_block(cuda):
