@@ -9,7 +9,8 @@
 //     ctz(cwr): no per-item counters.  Emits one GroupRec {ip, cw, a, b} per control word (a, b:
 //     bit-planes of token bytes - 1).
 //
-// Checks C1-C2 are applied exactly as by the oracle (oracle/qlz_oracle.c:180-231).
+// Check C1 is applied exactly as by the oracle (oracle/qlz_oracle.c:180-231); a
+// token cut by csize (C2) ends the item list in front of it, and K2's checks give the verdict.
 #pragma once
 #include "qlzx_decode_batch.h"
 
@@ -153,7 +154,22 @@ __device__ __forceinline__ void k1_parse_wave(uint8_t *ring, uint32_t lane, uint
                 const bool bad = (gb & (((int32_t)w >= 0) | (g >= gmax))) | (hasm & (q2 > csize)) |
                                  (hasm2 & (q2 + e2 + 1 > csize));
                 if (bad) {
-                    st = QLZX_E_CORRUPT;
+                    // C1 is final.  A token that runs past csize (C2) only ends the parse in front
+                    // of it: K2 then finds that the items stop short of dsize, or that the item
+                    // completing dsize does not end the stream (C5), which is the oracle's
+                    // E_CORRUPT as well -- but in a core padded to 9 bytes (quicklz.c:493) set
+                    // bits above the last item make tokens of the padding, which the oracle,
+                    // stopping at op == dsize, never reads: that stream is valid.
+                    if (gb) {
+                        st = QLZX_E_CORRUPT;
+                    } else {
+                        const bool first = q2 <= csize;  // the first token fits: the second is the cut one
+                        const uint32_t idx = __builtin_clz(cwr) + run;
+                        ra |= first ? (e & 1u) << idx : 0u;
+                        rb |= first ? (e >> 1) << idx : 0u;
+                        ip = first ? q2 : q;
+                        cwr = rest >> (first ? 1u : 0u);
+                    }
                     done_parse = true;
                     break;
                 }
@@ -164,7 +180,12 @@ __device__ __forceinline__ void k1_parse_wave(uint8_t *ring, uint32_t lane, uint
                     if (g > 0) {
                         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
                         const u32x4 rec = {rec_ip, cwg, ra, rb};
-                        asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(myrec + (g - 1)), "v"(rec) : "memory");
+                        // s_nop 1: two wait states before any VALU write of the store's data
+                        // registers (rec_ip .. rb are reassigned right below), which gfx940 and
+                        // later need after a store of more than 64 bits; the compiler's hazard
+                        // recogniser does not look into inline asm
+                        asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(myrec + (g - 1)), "v"(rec)
+                                     : "memory");
                     }
                     rec_ip = ip;
                     cwg = w;

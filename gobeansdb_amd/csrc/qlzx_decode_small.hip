@@ -9,7 +9,8 @@
 //   0. the stream is staged into LDS (zero past csize) straight from the request's slot;
 //   1. info[x] for every stream byte x: the outcome of parsing a control-word group at x --
 //      FULL (its 31 items fit: info = group length 35..128), END k (the stream ends before
-//      item k: the last group), BAD (no bit 31, check C1; a token past the end, check C2).
+//      item k, or item k is a token that runs past the end, check C2: the last group), BAD (no
+//      bit 31, check C1).
 //      Every x whose dword has bit 31 parses its group at once (candidates listed first, for balance);
 //   2. jump tables by pointer doubling: J2, J4, J8, J16 (u16 next-group position, 0: none);
 //   3. one lane hops J16 to list every 16th group start, then steps the last groups by info;
@@ -18,7 +19,7 @@
 //      qlzx_decode_solo.hip steps 4-8 (the checks C3-C5 included), with the literal bytes and
 //      sources in LDS and the result written once to the destination (the caller's slot).
 // Statuses and bytes equal the batch decoder's (K1 + K2, qlzx_decode_k1.h and qlzx_decode_k2.h) on the same stream,
-// dsize-0 rule included (tests/test_gpu_solo.py).
+// dsize-0 rule included (tests/test_gpu_solo.py; hand-assembled streams: tests/test_gpu_crafted_streams.py).
 #pragma once
 #include "qlzx_decode_batch.h"
 #include "qlzx_decode_solo.hip"  // kSoloWG, tok_code
@@ -213,8 +214,13 @@ __device__ __forceinline__ bool small_decode(SmallLds &L, const uint8_t *src, ui
 #endif
             }
             if (fin) {
-                const uint32_t ke = lim - ex;
-                L.p.info[x] = (uint8_t)(c > 3 ? kSmBad : ke <= min((uint32_t)__builtin_ctz(mrem | 0x80000000u), 30u) ? kSmEnd + ke : 35 + ex);
+                // a token that runs past csize (c > 3, check C2) ends the stream in front of it, at the
+                // item of the lowest bit left in mrem: the checks of step 5 then find the items short
+                // of dsize or the completing item not at the end (C5), as the oracle's E_CORRUPT; in
+                // a core padded to 9 bytes such a token can stand in the padding, behind the item
+                // that completes dsize, where the oracle never reads it
+                const uint32_t ke = lim - ex, kn = min((uint32_t)__builtin_ctz(mrem | 0x80000000u), 30u);
+                L.p.info[x] = (uint8_t)(c > 3 || ke <= kn ? kSmEnd + min(ke, kn) : 35 + ex);
                 i = atomicAdd(&L.cursor, 1u);
                 if (i < ncand) start();
             }
@@ -265,7 +271,7 @@ __device__ __forceinline__ bool small_decode(SmallLds &L, const uint8_t *src, ui
             const uint32_t e = L.p.info[x];
             L.glist[g++] = (uint16_t)x;
             if (sm_full(e)) { x += e; continue; }
-            if (e == kSmBad) { st = QLZX_E_CORRUPT; break; }  // C1 / C2
+            if (e == kSmBad) { st = QLZX_E_CORRUPT; break; }  // C1
             klast = e - kSmEnd;  // the stream ends inside this group
             break;
         }

@@ -28,7 +28,8 @@
 //   7. pointer jumping s[p] <- s[s[p]] over the whole block until every byte points at a
 //      literal (log2 of the longest copy chain rounds);
 //   8. gather: out[p] = out[s[p]] (the literal bytes written in 5).
-// Status and output equal K1 + K2b's on the same stream (tests/test_gpu_solo.py).
+// Status and output equal K1 + K2b's on the same stream (tests/test_gpu_solo.py; hand-assembled
+// streams: tests/test_gpu_crafted_streams.py).
 #pragma once
 #include "qlzx_decode_batch.h"
 
