@@ -14,6 +14,8 @@ depends on none of them.
   MUTATIONS            one edit each to a valid stream, giving an invalid one
   collection()         every valid stream of the families below, built once
   invalid_collection() the invalid ones
+  disassemble(stream)  (dsize, items, bail-out margins) of a valid stream: what an encoder decided
+  replay(stream, items)   the plaintext from a disassembly
 
 The forms (t is the little-endian token, tl its bytes):
   A  tl 1  t & 3 == 0                  off = t >> 2         (0..63)      ml = 3
@@ -661,3 +663,67 @@ def invalid_collection() -> tuple:
 
 
 Invalid = namedtuple("Invalid", "name kind family stream dsize")
+
+
+# ------------------------------------------------------------------ disassembler ----
+def disassemble(stream: bytes):
+    """(dsize, items, tests) of a valid level-3 stream -- what an encoder decided, read back.
+
+    items: (ip, form_bytes, length, offset) per item, ip the plaintext position it starts at;
+           a literal is (ip, 0, 1, 0).  None for a stored stream.
+    tests: one margin for every control word but the first that the encoder's main loop starts
+           (ip <= dsize - 11) past three quarters of the input (ip > 3 * (dsize >> 2)): the places
+           where quicklz.c:218 compares.  margin = (ip - (ip >> 5)) - op, op the core offset of
+           that control word (0 = the first byte after the header); the block stays compressed
+           while every margin is >= 0 (>= 9 under Go's rule, which counts the header)."""
+    s = stream
+    hdr = 9 if s[0] & 2 else 3
+    csize, dsize = ((int.from_bytes(s[1:5], "little"), int.from_bytes(s[5:9], "little")) if hdr == 9
+                    else (s[1], s[2]))
+    assert csize == len(s) and (s[0] >> 2) & 3 == 3, "not a whole level-3 stream"
+    if not s[0] & 1:
+        return dsize, None, []
+    items, tests = [], []
+    x, ip, cw, first = hdr, 0, 1, True
+    while ip < dsize:
+        if cw == 1:
+            if not first and ip <= dsize - 11 and ip > 3 * (dsize >> 2):
+                tests.append((ip - (ip >> 5)) - (x - hdr))
+            first = False
+            cw = int.from_bytes(s[x:x + 4], "little")
+            assert cw >> 31
+            x += 4
+        if cw & 1:
+            b0 = s[x]
+            tl = 1 if b0 & 3 == 0 else 2 if b0 & 3 != 3 else 3 if b0 & 127 != 3 else 4
+            t = int.from_bytes(s[x:x + tl], "little")
+            off, ml = ((t >> 2, 3) if tl == 1 or t & 3 == 1 else (t >> 6, (t >> 2 & 15) + 3) if tl == 2 else
+                       (t >> 7, (t >> 2 & 31) + 2) if tl == 3 else (t >> 15, (t >> 7 & 255) + 3))
+            items.append((ip, tl, ml, off))
+            ip += ml
+            x += tl
+        else:
+            items.append((ip, 0, 1, 0))
+            ip += 1
+            x += 1
+        cw >>= 1
+    assert ip == dsize and (x == csize or (x < hdr + 9 and csize == hdr + 9))
+    return dsize, items, tests
+
+
+def replay(stream: bytes, items) -> bytes:
+    """The plaintext from a disassembly: literals are read from the stream in item order."""
+    hdr = 9 if stream[0] & 2 else 3
+    out, x = bytearray(), hdr
+    for k, (ip, tl, ml, off) in enumerate(items):
+        if k % 31 == 0:
+            x += 4
+        assert ip == len(out)
+        if tl == 0:
+            out.append(stream[x])
+            x += 1
+        else:
+            seg = out[ip - off:ip - off + ml]
+            out += seg if off >= ml else (seg * (ml // off + 1))[:ml]
+            x += tl
+    return bytes(out)
