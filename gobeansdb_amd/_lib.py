@@ -36,6 +36,12 @@ HINT_CONSUMED, HINT_NUM_KEY, HINT_N_INDEX, HINT_DATASIZE, HINT_INDEX_OFF_LO, HIN
 HINT_NO_SPACE = 1
 HINT_SPLIT_CAP = 1 << 20        # store/config_default.go:28 (SplitCapStr "1M")
 HINT_INDEX_INTERVAL = 4 << 10   # store/config_default.go:29 (IndexIntervalSizeStr "4K")
+# qlzx_hint_merge_plan / qlzx_hint_merge_write: enum qlzx_hm_status (totals[8]) and the entries of
+# totals[12]; entries 1..8 sit where qlzx_hint_plan has them
+HM_OK, HM_NO_SPACE, HM_BAD_FILE, HM_TOO_MANY, HM_UNSORTED = range(5)
+HM_NAMES = ["HM_OK", "HM_NO_SPACE", "HM_BAD_FILE", "HM_TOO_MANY", "HM_UNSORTED"]
+HM_ITEMS_READ, HM_NUM_KEY, HM_N_INDEX, HM_DATASIZE, HM_INDEX_OFF_LO, HM_INDEX_OFF_HI, HM_BYTES_LO, HM_BYTES_HI, \
+    HM_STATUS, HM_STATUS_SOURCE, HM_N_COLLISION = range(11)
 MAX_NUM_CHUNK = 998   # store/data.go:15: the most destination chunks qlzx_gc_plan takes
 # QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
 # order, and one for every other answer
@@ -158,6 +164,12 @@ def lib() -> ctypes.CDLL:
     L.qlzx_hint_plan.restype = ctypes.c_int
     L.qlzx_hint_write.argtypes = [vp, u64, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, sz, vp]
     L.qlzx_hint_write.restype = ctypes.c_int
+    L.qlzx_hint_merge_workspace_size.argtypes = [u64, u32, u32]
+    L.qlzx_hint_merge_workspace_size.restype = sz
+    L.qlzx_hint_merge_plan.argtypes = [vp, u64, vp, vp, vp, u32, u32, ctypes.c_int64] + [vp] * 7 + [sz, vp]
+    L.qlzx_hint_merge_plan.restype = ctypes.c_int
+    L.qlzx_hint_merge_write.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.qlzx_hint_merge_write.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

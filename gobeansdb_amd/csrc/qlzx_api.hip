@@ -6,7 +6,8 @@
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
 // (replay, read, write, gc, hint) share qlzx_recfile.h; read also uses replay's k_rp_crc_long,
-// ScatterComp and finish kernels.
+// ScatterComp and finish kernels, and qlzx_hintmerge.hip uses qlzx_hint.hip's sort, run, index and
+// file kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +33,7 @@
 #include "qlzx_write.hip"
 #include "qlzx_gc.hip"
 #include "qlzx_hint.hip"
+#include "qlzx_hintmerge.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -521,6 +523,44 @@ int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
     f.vhash = vhash, f.item_rec = item_rec, f.index_item = index_item, f.item_hash = item_hash, f.item_off = item_off;
     f.chunk_id = chunk_id;
     return launched("qlzx_hint_write", qlzx::launch_hint_write(f, out, out_cap, totals, (hipStream_t)stream));
+}
+
+size_t qlzx_hint_merge_workspace_size(uint64_t bytes, uint32_t n_files, uint32_t cap) {
+    (void)bytes;
+    return qlzx::hm_ws_layout(n_files, cap, nullptr, nullptr);
+}
+
+int qlzx_hint_merge_plan(const uint8_t *hints, uint64_t bytes, const uint64_t *file_off, const uint64_t *file_len,
+                         const uint32_t *file_chunk, uint32_t n_files, uint32_t cap, int64_t index_interval,
+                         uint64_t *item_src, uint32_t *item_chunk, uint64_t *item_off, uint32_t *index_item,
+                         uint32_t *coll_item, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+    if (n_files == 0 || cap == 0) return QLZX_R_OK;
+    if ((!hints && bytes) || !file_off || !file_len || !file_chunk || !item_src || !item_chunk || !item_off ||
+        !index_item || !coll_item || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_hint_merge_plan: null arg");
+    if (int r = check_workspace("qlzx_hint_merge_plan", workspace, workspace_bytes,
+                                qlzx_hint_merge_workspace_size(bytes, n_files, cap)))
+        return r;
+    const qlzx::HmIn in{hints, bytes, file_off, file_len, file_chunk, n_files, cap};
+    return launched("qlzx_hint_merge_plan", qlzx::launch_hm_plan(in, index_interval, item_src, item_chunk, item_off,
+                    index_item, coll_item, totals, workspace, (hipStream_t)stream));
+}
+
+int qlzx_hint_merge_write(const uint8_t *hints, uint64_t bytes, uint32_t cap, const uint64_t *item_src,
+                          const uint32_t *item_chunk, const uint64_t *item_off, const uint32_t *index_item,
+                          uint8_t *out, uint64_t out_cap, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    if ((!hints && bytes) || !item_src || !item_chunk || !item_off || !index_item || (!out && out_cap) || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_hint_merge_write: null arg");
+    if ((uintptr_t)out & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_hint_merge_write: out is not 16-B aligned");
+    // the plan's workspace, for one source at the least (the write itself keeps nothing in it)
+    if (int r = check_workspace("qlzx_hint_merge_write", workspace, workspace_bytes,
+                                qlzx_hint_merge_workspace_size(bytes, 1, cap)))
+        return r;
+    const qlzx::HmFile f{hints, bytes, item_src, item_off, item_chunk, index_item};
+    return launched("qlzx_hint_merge_write", qlzx::launch_hm_write(f, cap, out, out_cap, totals, (hipStream_t)stream));
 }
 
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,

@@ -114,6 +114,7 @@ struct HintIn {
     const uint64_t *rec_off;
     const int32_t *hdr;
     uint32_t cap;
+    __device__ __forceinline__ uint32_t key(uint32_t r, const uint8_t **k) const;
 };
 // The key of record r, or ksz = 0 when a guard fails (nothing past the failing check is read).
 __device__ __forceinline__ uint32_t hint_key(const HintIn &in, uint32_t r, const uint8_t **key) {
@@ -125,6 +126,7 @@ __device__ __forceinline__ uint32_t hint_key(const HintIn &in, uint32_t r, const
     *key = in.data + off + kRpHdr;
     return ksz;
 }
+__device__ __forceinline__ uint32_t HintIn::key(uint32_t r, const uint8_t **k) const { return hint_key(*this, r, k); }
 // memcmp order with the shorter prefix first (Go's string <): < 0, 0, > 0.
 __device__ int hint_key_cmp(const uint8_t *a, uint32_t na, const uint8_t *b, uint32_t nb) {
     const uint32_t n = na < nb ? na : nb;
@@ -174,7 +176,9 @@ __global__ void __launch_bounds__(256) k_hint_compact(const uint64_t *hash, cons
 // fl[i]: bit 0 = first of its run of equal keyhash, bit 1 = same keyhash as its predecessor but
 // other key bytes (such a run is listed for k_hint_fix).  gh[i] = a group (one item) starts here,
 // val_r = the records in (keyhash, key, append) order: both final for every run without bit 1.
-__global__ void __launch_bounds__(256) k_hint_runs(HintIn in, const uint64_t *key_s, const uint32_t *val_s,
+// K names the keys: K::key(r, &bytes) = the length (qlzx_hintmerge.hip sorts hint items with it).
+template <class K>
+__global__ void __launch_bounds__(256) k_hint_runs(K in, const uint64_t *key_s, const uint32_t *val_s,
                                                    uint8_t *fl, uint8_t *gh, uint32_t *val_r, uint32_t *list,
                                                    HintCounters *cnt) {
     const uint32_t nv = cnt->nv;
@@ -184,7 +188,7 @@ __global__ void __launch_bounds__(256) k_hint_runs(HintIn in, const uint64_t *ke
         bool kdiff = false;
         if (!head) {
             const uint8_t *a, *b;
-            const uint32_t na = hint_key(in, val_s[i - 1], &a), nb = hint_key(in, r, &b);
+            const uint32_t na = in.key(val_s[i - 1], &a), nb = in.key(r, &b);
             kdiff = hint_key_cmp(a, na, b, nb) != 0;
         }
         fl[i] = (uint8_t)(head | (kdiff << 1));
@@ -197,8 +201,9 @@ __global__ void __launch_bounds__(256) k_hint_runs(HintIn in, const uint64_t *ke
 // The slow path: a run of equal keyhash with different keys (a 64-bit collision, or a caller's
 // keyhash array).  Every listed position finds its run; the run's first listed position ranks it:
 // lane by lane, an element's place is the number of elements before it in (key, append) order,
-// L^2 key comparisons for a run of L.
-__global__ void __launch_bounds__(256) k_hint_fix(HintIn in, const uint32_t *val_s, const uint8_t *fl, uint8_t *gh,
+// L^2 key comparisons for a run of L.  A run's positions are in append order (the sort is stable).
+template <class K>
+__global__ void __launch_bounds__(256) k_hint_fix(K in, const uint32_t *val_s, const uint8_t *fl, uint8_t *gh,
                                                   uint32_t *val_r, const uint32_t *list, const HintCounters *cnt) {
     const uint32_t nv = cnt->nv, nl = cnt->nlist < nv ? cnt->nlist : nv, lane = threadIdx.x & 63;
     for (uint32_t e = blockIdx.x * 4 + threadIdx.x / 64; e < nl; e += gridDim.x * 4) {
@@ -218,16 +223,16 @@ __global__ void __launch_bounds__(256) k_hint_fix(HintIn in, const uint32_t *val
         for (uint32_t a = s + lane; a < end; a += 64) {
             const uint32_t ra = val_s[a];
             const uint8_t *ka;
-            const uint32_t na = hint_key(in, ra, &ka);
+            const uint32_t na = in.key(ra, &ka);
             uint32_t rank = 0;
             bool dup = false;
             for (uint32_t b = s; b < end; b++) {
                 const uint32_t rb = val_s[b];
                 const uint8_t *kb;
-                const uint32_t nb = hint_key(in, rb, &kb);
+                const uint32_t nb = in.key(rb, &kb);
                 const int c = hint_key_cmp(kb, nb, ka, na);
-                rank += c < 0 || (c == 0 && rb < ra);
-                dup |= c == 0 && rb < ra;
+                rank += c < 0 || (c == 0 && b < a);
+                dup |= c == 0 && b < a;
             }
             val_r[s + rank] = ra;
             gh[s + rank] = !dup;
@@ -365,6 +370,8 @@ struct HintFile {
     const uint32_t *item_rec, *index_item;
     const uint64_t *item_hash, *item_off;
     uint32_t chunk_id;
+    // totals[8] after the write: whether the file fits is all this writer reports
+    __device__ __forceinline__ uint32_t status(uint32_t, bool fits) const { return fits ? 0u : 1u; }
 };
 struct HintTot {  // the plan's totals: items, index entries, datasize, indexOffset, file bytes
     uint32_t nk, nidx, datasize;
@@ -413,8 +420,10 @@ __device__ __forceinline__ uint32_t hint_index_dword(const HintFile &f, const Hi
     const uint64_t x = k < t.nk ? (r < 8 ? f.item_hash[k] : f.item_off[k]) : 0;
     return (uint32_t)(x >> (8 * (r & 4)));
 }
-// The file's dword at byte position p >= 16 (bytes past the file's end come out as zeros).
-__device__ __forceinline__ uint32_t hint_file_dword(const HintFile &f, const HintTot &t, uint64_t p, HintCur &c) {
+// The file's dword at byte position p >= 16 (bytes past the file's end come out as zeros).  F is
+// HintFile or another source of items with its own hint_cur_load and hint_index_dword.
+template <class F>
+__device__ __forceinline__ uint32_t hint_file_dword(const F &f, const HintTot &t, uint64_t p, HintCur &c) {
     if (p >= t.io) {
         const uint64_t d = p - t.io;
         const uint32_t lo = hint_index_dword(f, t, d & ~3ull);
@@ -449,13 +458,14 @@ __device__ __forceinline__ uint32_t hint_file_dword(const HintFile &f, const Hin
 // by a binary search over item_off, then four dwords and one aligned 16-B store (the file's last,
 // partial chunk: dwords, then at most three single bytes).  Nothing is written when the file does
 // not fit out_cap; totals[8] says so.
-__global__ void __launch_bounds__(256) k_hint_file(const HintFile f, uint32_t cap, uint8_t *out, uint64_t out_cap,
+template <class F>
+__global__ void __launch_bounds__(256) k_hint_file(const F f, uint32_t cap, uint8_t *out, uint64_t out_cap,
                                                    uint32_t *totals) {
     const HintTot t{totals[1] < cap ? totals[1] : cap, totals[2] < cap ? totals[2] : cap, totals[3],
                     (uint64_t)totals[4] | ((uint64_t)totals[5] << 32),
                     (uint64_t)totals[6] | ((uint64_t)totals[7] << 32)};
     const bool fits = t.fb <= out_cap;
-    if (blockIdx.x == 0 && threadIdx.x == 0) totals[8] = fits ? 0u : 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) totals[8] = f.status(totals[8], fits);
     // a file the arrays cannot describe (totals not the plan's) is cut to what they can
     if (!fits || t.nk == 0 || t.io < kHintHead || t.fb < t.io || t.fb - t.io > 16ull * t.nidx) return;
     const uint64_t nchunks = (t.fb + 15) / 16;
@@ -505,13 +515,12 @@ struct HintWs {
     void *tmp;
     size_t tmp_bytes;
 };
-inline size_t hint_ws_layout(uint32_t cap, uint8_t *base, HintWs *w) {
-    const size_t m = (size_t)cap + 2;
-    // rocPRIM's temporary storage for every count the calls may sort or scan (cap - first and one
-    // more): it is not monotone in the count (a small input takes another algorithm), so the
-    // largest need over cap + 1 and every power of two below it
+// rocPRIM's temporary storage for every count up to `most` that a call may sort or scan: it is not
+// monotone in the count (a small input takes another algorithm), so the largest need over `most`
+// and every power of two below it
+inline size_t hint_tmp_bytes(size_t most) {
     size_t tmp_bytes = 0;
-    for (size_t q = (size_t)cap + 1; q; q = q & (q - 1) ? (size_t)1 << (63 - __builtin_clzll(q)) : q >> 1) {
+    for (size_t q = most; q; q = q & (q - 1) ? (size_t)1 << (63 - __builtin_clzll(q)) : q >> 1) {
         size_t sort_tmp = 0, scan_tmp = 0, acc_tmp = 0;
         (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr,
                                         (const uint32_t *)nullptr, (uint32_t *)nullptr, q, 0, 64);
@@ -521,6 +530,11 @@ inline size_t hint_ws_layout(uint32_t cap, uint8_t *base, HintWs *w) {
                                       q, HintAccPlus());
         tmp_bytes = std::max(tmp_bytes, std::max(std::max(sort_tmp, scan_tmp), acc_tmp));
     }
+    return tmp_bytes;
+}
+inline size_t hint_ws_layout(uint32_t cap, uint8_t *base, HintWs *w) {
+    const size_t m = (size_t)cap + 2;
+    const size_t tmp_bytes = hint_tmp_bytes((size_t)cap + 1);  // the calls take cap - first and one more
     WsCarver c{base};
     HintWs t;
     t.cnt = c.take<HintCounters>(sizeof(HintCounters));
@@ -573,9 +587,9 @@ inline int launch_hint_plan(const HintIn &in, const uint32_t *result, const uint
                                   (size_t)M, 0, 64, s);
     if (e != hipSuccess) return (int)e;
     // (keyhash, key, append) order and the groups
-    hipLaunchKernelGGL(k_hint_runs, G, B, 0, s, in, (const uint64_t *)w.key_s, (const uint32_t *)w.val_s, w.fl, w.gh,
+    hipLaunchKernelGGL(k_hint_runs<HintIn>, G, B, 0, s, in, (const uint64_t *)w.key_s, (const uint32_t *)w.val_s, w.fl, w.gh,
                        w.val_r, w.list, w.cnt);
-    hipLaunchKernelGGL(k_hint_fix, dim3(1024), B, 0, s, in, (const uint32_t *)w.val_s, (const uint8_t *)w.fl, w.gh,
+    hipLaunchKernelGGL(k_hint_fix<HintIn>, dim3(1024), B, 0, s, in, (const uint32_t *)w.val_s, (const uint8_t *)w.fl, w.gh,
                        w.val_r, (const uint32_t *)w.list, (const HintCounters *)w.cnt);
     // the cut
     if ((e = hipMemsetAsync(w.fa, 0, 4 * (size_t)M, s)) != hipSuccess) return (int)e;
@@ -612,7 +626,7 @@ inline int launch_hint_plan(const HintIn &in, const uint32_t *result, const uint
 inline int launch_hint_write(const HintFile &f, uint8_t *out, uint64_t out_cap, uint32_t *totals, hipStream_t s) {
     // 16 + 289 (n - first) bytes at the most: 23 + 250 of an item and 16 of its index entry
     const uint64_t chunks = ((uint64_t)kHintHead + 289ull * f.in.cap + 15) / 16;
-    hipLaunchKernelGGL(k_hint_file, dim3(grid_for(chunks, 256, 2048)), dim3(256), 0, s, f, f.in.cap, out, out_cap, totals);
+    hipLaunchKernelGGL(k_hint_file<HintFile>, dim3(grid_for(chunks, 256, 2048)), dim3(256), 0, s, f, f.in.cap, out, out_cap, totals);
     return (int)hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-"""Hint split files of a replayed chunk on the GPU.
+"""Hint split files of a replayed chunk, and their merge, on the GPU.
 
 What buildHintFromData (store/bucket.go:89-117) does with the records of a replay:
 getKeyHash of each key (store/key.go:41-59), HintBuffer.Set in append order (store/hint.go:
@@ -6,11 +6,20 @@ getKeyHash of each key (store/key.go:41-59), HintBuffer.Set in append order (sto
 SplitCap items exist and opens the next split), HintBuffer.Dump's sort by (keyhash, key) and
 hintFileWriter's file: head, items and the sparse index (store/hintfile.go:142-212).  Every
 per-record step runs in libqlzx.so (qlzx_keyhash_batch, qlzx_hint_plan, qlzx_hint_write,
-csrc/qlzx_hint.hip); the host reads back totals[10] once per split.  The HTree, the hint lookup
-structures and hint merge stay out of scope; the caller owns the files' bytes.
+csrc/qlzx_hint.hip); the host reads back totals[10] once per split.
+
+What hintMgr.Merge (store/hint.go:455-508) does with those files: merge (store/hintmerge.go:96-159)
+over every split of a bucket gives the one merged file that lookups search first and the items
+whose keyhash two or more keys share (the collision table GC's isNewest needs).  merge() takes the
+files as device tensors, straight from build(); every per-item step runs in libqlzx.so
+(qlzx_hint_merge_plan, qlzx_hint_merge_write, csrc/qlzx_hintmerge.hip); the host reads back
+totals[12] once, and the collision items when there are any.  CollisionTable.compareAndSet against
+an existing table, the HTree and key lookups through hint files stay out of scope; the caller owns
+the files' bytes.
 """
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 
 import numpy as np
@@ -114,3 +123,102 @@ def build(res: replay.ReplayResult, split_cap: int = SPLIT_CAP, index_interval: 
         first += sp.consumed
         max_offset = sp.datasize
     return out
+
+
+@dataclass
+class HintMerged:
+    file: torch.Tensor   # uint8 (device): the merged file's bytes; empty when write=False
+    num_key: int
+    datasize: int        # the largest of the sources' heads'
+    index_offset: int
+    n_index: int
+    items_read: int      # the items of all sources
+    collisions: list     # (keyhash, key, chunk_id, offset, ver, vhash) of every merged item whose keyhash
+    #                      is shared by two or more keys, in merged order
+
+
+def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_interval: int = INDEX_INTERVAL,
+                 write: bool = True, cap: int | None = None, workspace: batch.Workspace | None = None,
+                 stream=None) -> HintMerged:
+    """merge() for a caller that holds every source in one device buffer: source i is
+    hints[file_off[i] : file_off[i] + file_len[i]] with the reader's chunk id chunk_ids[i].
+    cap (the most items the sources may hold) defaults to what their lengths allow."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return merge_packed(hints, file_off, file_len, chunk_ids, index_interval, write, cap, workspace, None)
+    L = _lib.lib()
+    dev = hints.device
+    lens = [int(x) for x in file_len]
+    n_files, nbytes = len(lens), int(hints.numel())
+    if not (len(file_off) == len(chunk_ids) == n_files):
+        raise ValueError("merge: one offset, length and chunk id per source")
+    room = sum(max(x - 16, 0) for x in lens)
+    if cap is None:
+        cap = room // 23
+    empty = torch.empty(0, dtype=torch.uint8, device=dev)
+    if n_files == 0:
+        return HintMerged(empty, 0, 0, 16, 0, 0, [])
+    cap = max(cap, 1)                               # a source without room for an item is the device's verdict
+    out_cap = 16 + room + 16 * cap if write else 0  # always enough: no read-back before the write
+    st_ = batch._stream()
+    u64 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.uint64).view(np.int64)).to(dev)
+    off_d, len_d = u64([int(x) for x in file_off]), u64(lens)
+    chunk_d = torch.from_numpy(np.asarray([int(c) & 0xFFFFFFFF for c in chunk_ids],
+                                          dtype=np.uint32).view(np.int32)).to(dev)
+    item_src, item_off = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(2))
+    item_chunk, index_item, coll_item = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+    totals = torch.zeros(12, dtype=torch.int32, device=dev)
+    out = torch.empty(out_cap, dtype=torch.uint8, device=dev)
+    ws_bytes = L.qlzx_hint_merge_workspace_size(nbytes, n_files, cap)
+    ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
+    hp = batch._ptr(hints) if nbytes else None
+    _lib.check(L.qlzx_hint_merge_plan(hp, nbytes, off_d.data_ptr(), len_d.data_ptr(), chunk_d.data_ptr(), n_files, cap,
+                                      index_interval, item_src.data_ptr(), item_chunk.data_ptr(), item_off.data_ptr(),
+                                      index_item.data_ptr(), coll_item.data_ptr(), totals.data_ptr(), ws.data_ptr(),
+                                      ws_bytes, st_), "qlzx_hint_merge_plan")
+    if write:
+        _lib.check(L.qlzx_hint_merge_write(hp, nbytes, cap, item_src.data_ptr(), item_chunk.data_ptr(),
+                                           item_off.data_ptr(), index_item.data_ptr(), out.data_ptr(), out_cap,
+                                           totals.data_ptr(), ws.data_ptr(), ws_bytes, st_), "qlzx_hint_merge_write")
+    t = totals.cpu().numpy().view(np.uint32)        # the read-back
+    status = int(t[_lib.HM_STATUS])
+    if status != _lib.HM_OK:
+        name = _lib.HM_NAMES[status] if status < len(_lib.HM_NAMES) else str(status)
+        raise _lib.QlzxError(f"qlzx_hint_merge: {name}, source {int(t[_lib.HM_STATUS_SOURCE])}")
+    collisions = []
+    ncoll = int(t[_lib.HM_N_COLLISION])
+    if ncoll:
+        # the collision items' 23 + 255 source bytes, gathered on the device: one more read-back
+        ci = coll_item[:ncoll].long()
+        src = item_src[ci]
+        span = (src[:, None] + torch.arange(23 + 255, device=dev)[None, :]).clamp_(max=nbytes - 1)
+        raw = hints[span].cpu().numpy()
+        chunks = item_chunk[ci].cpu().numpy().view(np.uint32)
+        for row, c in zip(raw, chunks):
+            b = row.tobytes()
+            ksz = b[22]
+            collisions.append((int.from_bytes(b[0:8], "little"), b[23:23 + ksz], int(c),
+                               int.from_bytes(b[12:16], "little"), int.from_bytes(b[16:20], "little", signed=True),
+                               int.from_bytes(b[20:22], "little")))
+    nb = int(t[_lib.HM_BYTES_LO]) | (int(t[_lib.HM_BYTES_HI]) << 32)
+    return HintMerged(out[:nb] if write else empty, int(t[_lib.HM_NUM_KEY]), int(t[_lib.HM_DATASIZE]),
+                      int(t[_lib.HM_INDEX_OFF_LO]) | (int(t[_lib.HM_INDEX_OFF_HI]) << 32), int(t[_lib.HM_N_INDEX]),
+                      int(t[_lib.HM_ITEMS_READ]), collisions)
+
+
+def merge(files, chunk_ids, index_interval: int = INDEX_INTERVAL, write: bool = True,
+          workspace: batch.Workspace | None = None, stream=None) -> HintMerged:
+    """hintMgr.Merge over split files in device memory (HintSplit.file straight from build());
+    chunk_ids[i] is the chunk file i belongs to.  write=False is Merge(forGC = true): the collision
+    items and no file.  Raises QlzxError naming the status and the source for a file the reference's
+    readers would fail on (HM_BAD_FILE), or one that does not ascend strictly (HM_UNSORTED)."""
+    files = list(files)
+    if not files:
+        return merge_packed(torch.empty(0, dtype=torch.uint8), [], [], [], index_interval, write)
+    lens = [int(f.numel()) for f in files]
+    offs = [0] * len(files)
+    for i in range(1, len(files)):
+        offs[i] = offs[i - 1] + lens[i - 1]
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        hints = torch.cat([f.reshape(-1) for f in files])      # on the device: the files never leave it
+    return merge_packed(hints, offs, lens, chunk_ids, index_interval, write, None, workspace, stream)

@@ -519,6 +519,67 @@ int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
                     const uint64_t *item_off, const uint32_t *index_item, uint8_t *out, uint64_t out_cap,
                     uint32_t *totals /* in/out */, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The merged hint file of a bucket and its collision items, from split files resident in device
+ * memory: hintMgr.Merge (store/hint.go:455-508) -> merge / mergeWriter / mergeHeap.Less
+ * (store/hintmerge.go) over hintFileReader.open / next and hintFileWriter.writeItem / close
+ * (store/hintfile.go:57-212).  Conventions as the other qlzx_hint_* calls: device pointers only
+ * (file_off / file_len / file_chunk included, one entry per source), nothing allocates, every
+ * launch goes on `stream`, no host synchronisation and no read-back between plan and write, one
+ * workspace of qlzx_hint_merge_workspace_size bytes serves both calls.
+ * Source i is the bytes hints[file_off[i] .. + file_len[i]) at any alignment, file_chunk[i] its
+ * reader's chunkID.
+ *   - reading: head {indexOffset i64, numKey u32, datasize u32}; indexOffset == 0 means "no index"
+ *     and the items run to the file's end; numKey is not used; an item starts at every offset from
+ *     16 on below indexOffset: 23 bytes {keyhash u64, chunk u32, offset u32, ver i32, vhash u16,
+ *     ksz u8} and ksz key bytes.  An item that starts below indexOffset and ends inside the file is
+ *     read whole.  The stored chunk is ignored: the item's position is (file_chunk[i], offset).
+ *   - QLZX_HM_BAD_FILE (totals[9] = the lowest such source): file_len < 16, the source runs past
+ *     `bytes`, indexOffset negative or > file_len, an item ends past the file, or no item at all
+ *     (merge dereferences a nil first item; no writer dumps an empty buffer).
+ *   - merged items: one per distinct (keyhash, key bytes); among equal keys the largest CmpKey =
+ *     chunk << 32 | offset wins (unsigned), on a tie the later source, then the later item; items
+ *     ascend by keyhash, then by key bytes, the shorter prefix first.  For sources that ascend
+ *     strictly by (keyhash, key) this is what the heap merge produces.  A source whose adjacent
+ *     items do not ascend strictly is refused: QLZX_HM_UNSORTED (totals[9] = the lowest one).
+ *   - QLZX_HM_TOO_MANY: the sources hold more than cap items.  Precedence: BAD_FILE, TOO_MANY,
+ *     UNSORTED; with any of them numKey, index entries, file bytes and collision items are 0 and
+ *     qlzx_hint_merge_write writes nothing and keeps the status.
+ *   - collisions (mergeWriter.flush): every merged item whose keyhash is shared by two or more
+ *     distinct keys, in merged order; CollisionTable.compareAndSet stays the caller's.
+ *   - file: head with datasize = the largest of the sources' heads'; per item its 23 + ksz source
+ *     bytes with bytes 8..11 replaced by item_chunk; indexOffset and the sparse index as
+ *     qlzx_hint_plan states them.
+ * The sources' own index sections only cut the (serial) walk over a source into stretches, and only
+ * once proven: entries strictly increasing inside [16, indexOffset), every walk landing exactly on
+ * the next entry, the last one reaching indexOffset.  A source that fails, or has no index, is
+ * walked from 16 by one lane: correct, not fast.  The result never depends on an index section.
+ * Whatever the bytes hold, every load stays inside hints[0, bytes) and the arrays' cap entries,
+ * every store inside the arrays and out_cap, and every walk advances 23 bytes or more per step. */
+enum qlzx_hm_status { QLZX_HM_OK = 0, QLZX_HM_NO_SPACE, QLZX_HM_BAD_FILE, QLZX_HM_TOO_MANY, QLZX_HM_UNSORTED };
+/* Workspace of the two qlzx_hint_merge_* calls (`bytes` does not enter it today). */
+size_t qlzx_hint_merge_workspace_size(uint64_t bytes, uint32_t n_files, uint32_t cap);
+/* The plan; alone it is Merge(forGC = true): the collision items and no file.  cap = the capacity
+ * of every per-item array.
+ *   item_src[k]: the byte offset in `hints` of the source item that became merged item k;
+ *   item_chunk[k]: its chunk id; item_off[k]: its offset in the merged file; index_item[m]: the
+ *   item of index entry m; coll_item[c]: the merged item of collision item c, ascending.
+ *   totals[12] = {items read, numKey, index entries, datasize, indexOffset (lo, hi), file bytes
+ *   (lo, hi), status, the source the status names, collision items, 0}.
+ * n_files == 0 or cap == 0 returns QLZX_R_OK; nothing is launched or written. */
+int qlzx_hint_merge_plan(const uint8_t *hints, uint64_t bytes, const uint64_t *file_off, const uint64_t *file_len,
+                         const uint32_t *file_chunk, uint32_t n_files, uint32_t cap, int64_t index_interval,
+                         uint64_t *item_src, uint32_t *item_chunk, uint64_t *item_off, uint32_t *index_item,
+                         uint32_t *coll_item, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                         void *stream);
+/* The file, after qlzx_hint_merge_plan: totals[6,7] bytes from `out` on.  `out` is 16-B aligned
+ * and need not be zeroed; no byte past the file's is written.  If the file exceeds out_cap nothing
+ * is written and totals[8] = QLZX_HM_NO_SPACE; a status of the plan stays.  16 + 39 cap + 22 bytes
+ * always suffice when cap = (the sum of file_len - 16) / 23.  cap == 0 returns QLZX_R_OK. */
+int qlzx_hint_merge_write(const uint8_t *hints, uint64_t bytes, uint32_t cap, const uint64_t *item_src,
+                          const uint32_t *item_chunk, const uint64_t *item_off, const uint32_t *index_item,
+                          uint8_t *out, uint64_t out_cap, uint32_t *totals /* in/out */, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* Getvhash (store/item.go:89-100, Fnv1a of utils/hash.go:8-16) of n values. */
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,
                      void *stream);
