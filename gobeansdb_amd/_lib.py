@@ -42,7 +42,14 @@ HM_OK, HM_NO_SPACE, HM_BAD_FILE, HM_TOO_MANY, HM_UNSORTED = range(5)
 HM_NAMES = ["HM_OK", "HM_NO_SPACE", "HM_BAD_FILE", "HM_TOO_MANY", "HM_UNSORTED"]
 HM_ITEMS_READ, HM_NUM_KEY, HM_N_INDEX, HM_DATASIZE, HM_INDEX_OFF_LO, HM_INDEX_OFF_HI, HM_BYTES_LO, HM_BYTES_HI, \
     HM_STATUS, HM_STATUS_SOURCE, HM_N_COLLISION = range(11)
-MAX_NUM_CHUNK = 998   # store/data.go:15: the most destination chunks qlzx_gc_plan takes
+# qlzx_hint_lookup: enum qlzx_hl_status (per request), the entries of totals[4], file_flags and flags
+HL_MISS, HL_FOUND, HL_ERR, HL_BAD_FILE = range(4)
+HL_NAMES = ["HL_MISS", "HL_FOUND", "HL_ERR", "HL_BAD_FILE"]
+HL_N_FOUND, HL_N_MISS, HL_N_ERR, HL_N_BAD_FILE = range(4)
+HL_FILE_MERGED = 1
+HL_F_BOUNDED, HL_F_LANE, HL_F_WAVE = 1, 2, 4
+HL_LANE_FROM = 16384            # QLZX_HL_LANE_FROM: a lane per request from this many on
+MAX_NUM_CHUNK = 998  # store/data.go:15: the most destination chunks qlzx_gc_plan takes
 # QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
 # order, and one for every other answer
 NC_AUDIO_BASIC, NC_AUDIO_AIFF, NC_AUDIO_MPEG, NC_APPLICATION_OGG, NC_AUDIO_MIDI, NC_VIDEO_AVI, NC_AUDIO_WAVE, \
@@ -170,6 +177,10 @@ def lib() -> ctypes.CDLL:
     L.qlzx_hint_merge_plan.restype = ctypes.c_int
     L.qlzx_hint_merge_write.argtypes = [vp, u64, u32, vp, vp, vp, vp, vp, u64, vp, vp, sz, vp]
     L.qlzx_hint_merge_write.restype = ctypes.c_int
+    L.qlzx_hint_lookup_workspace_size.argtypes = [u32, u32]
+    L.qlzx_hint_lookup_workspace_size.restype = sz
+    L.qlzx_hint_lookup.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32] + [vp] * 9 + [sz, vp]
+    L.qlzx_hint_lookup.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

@@ -6,8 +6,8 @@
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
 // (replay, read, write, gc, hint) share qlzx_recfile.h; read also uses replay's k_rp_crc_long,
-// ScatterComp and finish kernels, and qlzx_hintmerge.hip uses qlzx_hint.hip's sort, run, index and
-// file kernels.
+// ScatterComp and finish kernels, qlzx_hintmerge.hip uses qlzx_hint.hip's sort, run, index and
+// file kernels, and qlzx_hintlookup.hip its key hash and qlzx_hintmerge.hip's loads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +34,7 @@
 #include "qlzx_gc.hip"
 #include "qlzx_hint.hip"
 #include "qlzx_hintmerge.hip"
+#include "qlzx_hintlookup.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -561,6 +562,34 @@ int qlzx_hint_merge_write(const uint8_t *hints, uint64_t bytes, uint32_t cap, co
         return r;
     const qlzx::HmFile f{hints, bytes, item_src, item_off, item_chunk, index_item};
     return launched("qlzx_hint_merge_write", qlzx::launch_hm_write(f, cap, out, out_cap, totals, (hipStream_t)stream));
+}
+
+size_t qlzx_hint_lookup_workspace_size(uint32_t n, uint32_t n_files) {
+    return qlzx::hl_ws_layout(n, n_files, nullptr, nullptr);
+}
+
+int qlzx_hint_lookup(const uint8_t *hints, uint64_t bytes, const uint64_t *file_off, const uint64_t *file_len,
+                     const uint32_t *file_chunk, const uint32_t *file_flags, uint32_t n_files, const uint8_t *keys,
+                     const uint64_t *key_off, const uint32_t *key_len, const uint64_t *keyhash, uint32_t n,
+                     uint32_t flags, int32_t *status, uint32_t *hit_file, uint32_t *chunk, uint32_t *offset,
+                     int32_t *ver, uint16_t *vhash, uint64_t *item_src, uint32_t *totals, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+    if (n == 0 || n_files == 0) return QLZX_R_OK;
+    // keyhash may be null: the default hash of the request's key
+    if ((!hints && bytes) || !file_off || !file_len || !file_chunk || !file_flags || !keys || !key_off || !key_len ||
+        !status || !hit_file || !chunk || !offset || !ver || !vhash || !item_src || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_hint_lookup: null arg");
+    constexpr uint32_t shapes = QLZX_HL_F_LANE | QLZX_HL_F_WAVE;
+    if ((flags & ~(QLZX_HL_F_BOUNDED | shapes)) || (flags & shapes) == shapes)
+        return fail(QLZX_R_BAD_ARG, "qlzx_hint_lookup: unknown flag, or both kernels named");
+    if (int r = check_workspace("qlzx_hint_lookup", workspace, workspace_bytes,
+                                qlzx_hint_lookup_workspace_size(n, n_files)))
+        return r;
+    const qlzx::HlIn in{hints, bytes, file_off, file_len, file_chunk, file_flags, n_files, keys, key_off, key_len,
+                        keyhash, n, (flags & QLZX_HL_F_BOUNDED) != 0};
+    const qlzx::HlOut out{status, hit_file, chunk, offset, ver, vhash, item_src, totals};
+    const bool lane = flags & shapes ? (flags & QLZX_HL_F_LANE) != 0 : n >= QLZX_HL_LANE_FROM;
+    return launched("qlzx_hint_lookup", qlzx::launch_hl(in, lane, out, workspace, (hipStream_t)stream));
 }
 
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,

@@ -1,4 +1,5 @@
-"""Hint split files of a replayed chunk, and their merge, on the GPU.
+"""Hint split files of a replayed chunk, their merge, and key lookups through them, on the GPU
+(SURVEY §8 f1c, f1d, f1e).
 
 What buildHintFromData (store/bucket.go:89-117) does with the records of a replay:
 getKeyHash of each key (store/key.go:41-59), HintBuffer.Set in append order (store/hint.go:
@@ -13,9 +14,16 @@ over every split of a bucket gives the one merged file that lookups search first
 whose keyhash two or more keys share (the collision table GC's isNewest needs).  merge() takes the
 files as device tensors, straight from build(); every per-item step runs in libqlzx.so
 (qlzx_hint_merge_plan, qlzx_hint_merge_write, csrc/qlzx_hintmerge.hip); the host reads back
-totals[12] once, and the collision items when there are any.  CollisionTable.compareAndSet against
-an existing table, the HTree and key lookups through hint files stay out of scope; the caller owns
-the files' bytes.
+totals[12] once, and the collision items when there are any.
+
+What hintMgr.getItem (store/hint.go:570-596) answers over those files: lookup() takes the files in
+the order getItem reaches them and a batch of keys, and returns per key where its record is
+(hintFileIndex.get, store/hintindex.go:28-69, as it is, or bounded=True: the scan ends at the
+index).  Every step runs in libqlzx.so (qlzx_hint_lookup, csrc/qlzx_hintlookup.hip); the results
+stay on the device (they feed replay.read_records / qlzx_read_plan), the host reads back totals[4].
+
+CollisionTable.compareAndSet against an existing table, the HTree and the in-memory
+HintBuffer.Get stay out of scope; the caller owns the files' bytes.
 """
 from __future__ import annotations
 
@@ -222,3 +230,80 @@ def merge(files, chunk_ids, index_interval: int = INDEX_INTERVAL, write: bool = 
     with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
         hints = torch.cat([f.reshape(-1) for f in files])      # on the device: the files never leave it
     return merge_packed(hints, offs, lens, chunk_ids, index_interval, write, None, workspace, stream)
+
+
+@dataclass
+class HintLookup:
+    status: torch.Tensor     # int32 [n] (device): _lib.HL_MISS / HL_FOUND / HL_ERR / HL_BAD_FILE
+    hit_file: torch.Tensor   # int32 [n]: the file where the search ended
+    chunk: torch.Tensor      # int32 [n] (u32 bits): a split hit's chunk id, a merged hit's stored chunk
+    offset: torch.Tensor     # int32 [n] (u32 bits): the record's offset in its chunk
+    ver: torch.Tensor        # int32 [n]
+    vhash: torch.Tensor      # int16 [n] (u16 bits)
+    item_src: torch.Tensor   # int64 [n]: the item's byte offset in the packed files
+    totals: tuple            # (found, miss, err, bad_file), read back once
+
+
+def lookup_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, keys: batch.BlockBatch,
+                  merged: int | None = None, bounded: bool = False, keyhash: torch.Tensor | None = None,
+                  workspace: batch.Workspace | None = None, stream=None) -> HintLookup:
+    """lookup() for a caller that holds every file in one device buffer: file i is
+    hints[file_off[i] : file_off[i] + file_len[i]] with the chunk id chunk_ids[i], in search order."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return lookup_packed(hints, file_off, file_len, chunk_ids, keys, merged, bounded, keyhash, workspace, None)
+    L = _lib.lib()
+    dev = keys.data.device
+    lens = [int(x) for x in file_len]
+    n_files, nbytes, n = len(lens), int(hints.numel()), keys.n
+    if not (len(file_off) == len(chunk_ids) == n_files):
+        raise ValueError("lookup: one offset, length and chunk id per file")
+    if merged is not None and not 0 <= merged < n_files:
+        raise ValueError("lookup: merged is the index of a file")
+    if keyhash is not None:
+        if keyhash.numel() != n:
+            raise ValueError("keyhash: one per key")
+        keyhash = keyhash.to(device=dev, dtype=torch.int64).contiguous()
+    status, hit_file, chunk, offset, ver = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(5))
+    vhash = torch.zeros(n, dtype=torch.int16, device=dev)
+    item_src = torch.zeros(n, dtype=torch.int64, device=dev)
+    if n == 0 or n_files == 0:                      # no file: every key is a miss
+        return HintLookup(status, hit_file, chunk, offset, ver, vhash, item_src, (0, n, 0, 0))
+    u64 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.uint64).view(np.int64)).to(dev)
+    u32 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.uint32).view(np.int32)).to(dev)
+    off_d, len_d = u64([int(x) for x in file_off]), u64(lens)
+    chunk_d = u32([int(c) & 0xFFFFFFFF for c in chunk_ids])
+    flag_d = u32([_lib.HL_FILE_MERGED if i == merged else 0 for i in range(n_files)])
+    totals = torch.zeros(4, dtype=torch.int32, device=dev)
+    ws_bytes = L.qlzx_hint_lookup_workspace_size(n, n_files)
+    ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
+    flags = _lib.HL_F_BOUNDED if bounded else 0     # the kernel (a wave or a lane per request) goes by n
+    _lib.check(L.qlzx_hint_lookup(batch._ptr(hints) if nbytes else None, nbytes, off_d.data_ptr(), len_d.data_ptr(),
+                                  chunk_d.data_ptr(), flag_d.data_ptr(), n_files, keys.data.data_ptr(),
+                                  keys.off.data_ptr(), keys.length.data_ptr(), batch._ptr(keyhash), n, flags,
+                                  status.data_ptr(), hit_file.data_ptr(), chunk.data_ptr(), offset.data_ptr(),
+                                  ver.data_ptr(), vhash.data_ptr(), item_src.data_ptr(), totals.data_ptr(),
+                                  ws.data_ptr(), ws_bytes, batch._stream()), "qlzx_hint_lookup")
+    t = totals.cpu().numpy().view(np.uint32)        # the read-back
+    return HintLookup(status, hit_file, chunk, offset, ver, vhash, item_src, tuple(int(x) for x in t))
+
+
+def lookup(files, chunk_ids, keys: batch.BlockBatch, merged: int | None = None, bounded: bool = False,
+           keyhash: torch.Tensor | None = None, workspace: batch.Workspace | None = None,
+           stream=None) -> HintLookup:
+    """hintMgr.getItem of every key over hint files in device memory (HintSplit.file / HintMerged.file
+    straight from build() / merge()).  THE ORDER OF `files` IS THE SEARCH ORDER: newest chunk first,
+    a chunk's splits last to first, the merged file where getItem reaches it; chunk_ids[i] is the
+    chunk of file i, merged the index of the merged file (its hits report the chunk stored in the
+    item, and nothing after it is searched) or None.  bounded=False is the reference as it is: a
+    key above a file's last item usually ends in HL_ERR, which ends the search; bounded=True ends
+    the scan at the index and goes on to the next file (what a multi-GET or a GC liveness pass
+    wants).  keyhash (int64 [n]) replaces the default key hash.  The results stay on the device; totals is read back once."""
+    files = list(files)
+    lens = [int(f.numel()) for f in files]
+    offs = [0] * len(files)
+    for i in range(1, len(files)):
+        offs[i] = offs[i - 1] + lens[i - 1]
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        hints = torch.cat([f.reshape(-1) for f in files]) if files else torch.empty(0, dtype=torch.uint8)
+    return lookup_packed(hints, offs, lens, chunk_ids, keys, merged, bounded, keyhash, workspace, stream)

@@ -580,6 +580,67 @@ int qlzx_hint_merge_write(const uint8_t *hints, uint64_t bytes, uint32_t cap, co
                           uint8_t *out, uint64_t out_cap, uint32_t *totals /* in/out */, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* Key lookups through hint files resident in device memory: hintMgr.getItem (store/hint.go:570-596)
+ * -> hintChunk.get (:270-296) -> hintFileIndex.get (store/hintindex.go:28-69) over
+ * hintFileReader.next (store/hintfile.go:89-124), n requests at once.  Conventions as the other
+ * qlzx_hint_* calls: device pointers only, nothing allocates, every launch goes on `stream`, no
+ * host synchronisation and no read-back.
+ * The files are described as qlzx_hint_merge_plan's sources (one buffer, file_off / file_len at any
+ * alignment, file_chunk).  THE ORDER OF THE FILES IS THE SEARCH ORDER: a binding lists a bucket as
+ * getItem reaches it, newest chunk first, a chunk's splits last to first, the merged file where
+ * `i <= collisions.Chunk` first holds.  file_flags[i] & QLZX_HL_FILE_MERGED marks the merged file:
+ * a hit there reports the chunk stored in the item (a split hit reports file_chunk[i]), and no
+ * file after it is searched.  Request i is the key keys + key_off[i] .. + key_len[i] (any length;
+ * a key over 255 bytes equals no stored key and takes the same walk) with the hash keyhash[i], or,
+ * keyhash == NULL, getKeyHashDefalut of the key (qlzx_keyhash_batch's kernel, into the workspace).
+ * One file (hintFileIndex.get), every field little-endian and at any alignment:
+ *   - the index is the (file_len - indexOffset) / 16 entries {keyhash u64, offset i64} from
+ *     indexOffset on; j = sort.Search over them with Go's own loop (i, j = 0, n; h = (i + j) / 2;
+ *     entry h's keyhash < the wanted one moves i = h + 1, else j = h), so j is defined on unsorted
+ *     entries too.  The scan starts at entry j - 1's offset when j > 1, else at 16.
+ *   - the scan reads items {keyhash u64, chunk u32, offset u32, ver i32, vhash u16, ksz u8, key}
+ *     and ends after indexOffset - 16 bytes CONSUMED, not at indexOffset (after Seek the reader's
+ *     own offset is still 16): from a start above 16 it walks on into the index section and reads
+ *     index entries as items.  Per item: a 23-byte head or ksz key bytes that run past file_len are
+ *     QLZX_HL_ERR, decided before the item is compared; keyhash below the wanted one: next item;
+ *     above: QLZX_HL_MISS; equal: the key bytes decide between QLZX_HL_FOUND and the next item.
+ *   - QLZX_HL_ERR also answers an index entry's offset outside [16, file_len]: the reference's
+ *     behaviour there depends on the position its file descriptor was left at, and no writer
+ *     produces such an entry.
+ *   - QLZX_HL_BAD_FILE, what loadHintIndex would not have survived: file_len < 16, the file runs
+ *     past `bytes`, indexOffset outside [16, file_len], (file_len - indexOffset) % 16 != 0.
+ *   - QLZX_HL_ERR and QLZX_HL_BAD_FILE end that request's search (an error ends getItem), a hit
+ *     ends it, a miss goes on to the next file.  With files every writer produces, a key whose
+ *     hash lies above a file's last item usually ends in QLZX_HL_ERR once the file has two or more
+ *     index entries.
+ * flags: 0 is the reference as it is.  QLZX_HL_F_BOUNDED ends the scan at indexOffset by position
+ * (what the code meant): a key above the last item is a miss and the search goes on.
+ * Two kernels give the same results: a wave per request below QLZX_HL_LANE_FROM requests, a lane
+ * per request from there on (DESIGN.md §3.6 has the two measured).  QLZX_HL_F_WAVE or
+ * QLZX_HL_F_LANE (not both) names the kernel whatever n is.
+ * Per request: status[i]; hit_file[i] = the file where the search ended (the last one searched for
+ * a miss); for QLZX_HL_FOUND chunk / offset / ver / vhash of the item and item_src = its byte offset
+ * in `hints`, else those five are 0.  totals[4] = {found, miss, err, bad_file}.
+ * Whatever the bytes hold, every load stays inside hints[0, bytes) and inside the file being
+ * searched, every store inside the n entries of the outputs and totals[4], and every walk advances
+ * 23 bytes or more per step.
+ * n == 0 or n_files == 0 returns QLZX_R_OK and nothing is launched or written: without a file every
+ * request is a miss, and the outputs of that answer (all zero, totals {0, n, 0, 0}) are the
+ * caller's to set. */
+enum qlzx_hl_status { QLZX_HL_MISS = 0, QLZX_HL_FOUND, QLZX_HL_ERR, QLZX_HL_BAD_FILE };
+#define QLZX_HL_FILE_MERGED 1u
+#define QLZX_HL_F_BOUNDED 1u
+#define QLZX_HL_F_LANE 2u
+#define QLZX_HL_F_WAVE 4u
+#define QLZX_HL_LANE_FROM 16384u
+size_t qlzx_hint_lookup_workspace_size(uint32_t n, uint32_t n_files);
+int qlzx_hint_lookup(const uint8_t *hints, uint64_t bytes, const uint64_t *file_off, const uint64_t *file_len,
+                     const uint32_t *file_chunk, const uint32_t *file_flags, uint32_t n_files, const uint8_t *keys,
+                     const uint64_t *key_off, const uint32_t *key_len, const uint64_t *keyhash /* or NULL */,
+                     uint32_t n, uint32_t flags, int32_t *status, uint32_t *hit_file, uint32_t *chunk,
+                     uint32_t *offset, int32_t *ver, uint16_t *vhash, uint64_t *item_src, uint32_t *totals /* [4] */,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Getvhash (store/item.go:89-100, Fnv1a of utils/hash.go:8-16) of n values. */
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,
                      void *stream);
