@@ -62,8 +62,12 @@ static int fail_in(int code, const char *who, const char *what) {
 static int check_chunk_size(const char *who, uint64_t size) {
     return size / 256 >= 0xfffffff0ull ? fail_in(QLZX_R_BAD_ARG, who, "file too large") : QLZX_R_OK;
 }
+// every layout places its arrays at multiples of 256 from the base, so the base's own alignment is
+// what each array gets: 16 bytes, the widest access into any of them (qlzx.h, batch API preamble)
+static bool workspace_aligned(const void *workspace) { return (((uintptr_t)workspace) & 15u) == 0; }
 static int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, size_t need) {
-    return !workspace || workspace_bytes < need ? fail_in(QLZX_R_WORKSPACE, who, "workspace too small") : QLZX_R_OK;
+    if (!workspace || workspace_bytes < need) return fail_in(QLZX_R_WORKSPACE, who, "workspace too small");
+    return workspace_aligned(workspace) ? QLZX_R_OK : fail_in(QLZX_R_WORKSPACE, who, "workspace not 16-byte aligned");
 }
 // the tail of an entry point: e = what its launcher returned (a hipError_t)
 static int launched(const char *who, int e) { return e ? fail(QLZX_R_HIP, who, (hipError_t)e) : QLZX_R_OK; }
@@ -132,6 +136,8 @@ int qlzx_decompress_batch(const qlzx_blocks *b, const uint32_t *dst_cap, uint32_
     if (b->n == 0) return QLZX_R_OK;
     if (!b->src || !b->src_off || !b->src_len || !b->dst || !b->dst_off)
         return fail(QLZX_R_BAD_ARG, "qlzx_decompress_batch: null block array");
+    if (workspace && !workspace_aligned(workspace))
+        return fail(QLZX_R_WORKSPACE, "qlzx_decompress_batch: workspace not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     // no workspace: the general lane-per-block kernel for every block
     const bool fast = workspace && workspace_bytes >= qlzx::batch_layout(b->n, max_dsize).one;

@@ -16,6 +16,13 @@
  *    are device pointers; `stream` is a hipStream_t (NULL = default stream).
  *    Nothing here allocates: callers pass a workspace sized by the matching
  *    *_workspace_size() call, so launches are graph-capturable.
+ *    `workspace` must be 16-byte aligned: every layout places its arrays at
+ *    multiples of 256 bytes from the base, and the widest access into any of
+ *    them is 16 bytes (the decoder's GroupRec and BlkInfo records, the
+ *    level-1 tables' uint4 rows), so no layout needs more.  A non-null base that is
+ *    not 16-byte aligned returns QLZX_R_WORKSPACE before anything is launched.
+ *    Exactly workspace_bytes bytes from the base are the call's to use: no
+ *    byte before or past them is touched, and none needs a value on entry.
  *
  * Status codes reproduce the reference wrapper errors and add the
  * memory-safety checks the reference leaves out (quicklz.h:31 builds without
@@ -525,7 +532,8 @@ int qlzx_hint_write(const uint8_t *data, uint64_t size, const uint64_t *rec_off,
  * (store/hintfile.go:57-212).  Conventions as the other qlzx_hint_* calls: device pointers only
  * (file_off / file_len / file_chunk included, one entry per source), nothing allocates, every
  * launch goes on `stream`, no host synchronisation and no read-back between plan and write, one
- * workspace of qlzx_hint_merge_workspace_size bytes serves both calls.
+ * workspace of qlzx_hint_merge_workspace_size bytes serves both calls (no state is carried in it:
+ * the write itself keeps nothing in it).
  * Source i is the bytes hints[file_off[i] .. + file_len[i]) at any alignment, file_chunk[i] its
  * reader's chunkID.
  *   - reading: head {indexOffset i64, numKey u32, datasize u32}; indexOffset == 0 means "no index"

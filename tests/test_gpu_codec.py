@@ -315,23 +315,15 @@ def _tiny_blocks():
     return _TINY
 
 
-# (max_dsize, regions the ABI asks for, regions the caller gives)
-@pytest.mark.parametrize("crc", [False, True])
-@pytest.mark.parametrize("max_dsize,regions,given", [(2048, 2, 1), (16385, 3, 2)])
-def test_multi_chunk_under_provisioned_workspace(cuda, max_dsize, regions, given, crc):
-    """A caller may give fewer workspace regions than qlzx_decompress_workspace_size asks for.
-    Uniform sizes, two chunks, one region of two: every chunk's K1 and K2 run on the caller's
-    stream, one after another.  Mixed sizes, three chunks, two regions of three: K1 and K2 of
-    consecutive chunks overlap, but the last chunk's K1 does not start early.  Either way every
-    block decodes."""
+def _decode_tiny(max_dsize, ws_bytes, crc):
+    """One raw qlzx_decompress_batch call over _tiny_blocks() with a workspace of ws_bytes: every
+    block decodes (status, dsize, the CRC of each output against its plaintext's, and with crc the
+    fused CRC of each compressed value)."""
     import torch
     from gobeansdb_amd import _lib, batch
     t = _tiny_blocks()
     src, n = t["src"], t["src"].n
     L = _lib.lib()
-    full = L.qlzx_decompress_workspace_size(n, max_dsize)
-    assert full % regions == 0
-    ws_bytes = full // regions * given
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
     out = batch.BlockBatch.empty_for(t["lens"])
     dsize = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -350,6 +342,21 @@ def test_multi_chunk_under_provisioned_workspace(cuda, max_dsize, regions, given
     assert torch.equal(batch.crc32(out), t["plain_crc"])
     if crc:
         assert torch.equal(crc_out, t["src_crc"])
+
+
+# (max_dsize, regions the ABI asks for, regions the caller gives)
+@pytest.mark.parametrize("crc", [False, True])
+@pytest.mark.parametrize("max_dsize,regions,given", [(2048, 2, 1), (16385, 3, 2)])
+def test_multi_chunk_under_provisioned_workspace(cuda, max_dsize, regions, given, crc):
+    """A caller may give fewer workspace regions than qlzx_decompress_workspace_size asks for.
+    Uniform sizes, two chunks, one region of two: every chunk's K1 and K2 run on the caller's
+    stream, one after another.  Mixed sizes, three chunks, two regions of three: K1 and K2 of
+    consecutive chunks overlap, but the last chunk's K1 does not start early.  Either way every
+    block decodes."""
+    from gobeansdb_amd import _lib
+    full = _lib.lib().qlzx_decompress_workspace_size(_tiny_blocks()["src"].n, max_dsize)
+    assert full % regions == 0
+    _decode_tiny(max_dsize, full // regions * given, crc)
 
 
 def test_mixed_sizes_block_order_round_trip(cuda):

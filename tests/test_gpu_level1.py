@@ -13,12 +13,16 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.fixture(scope="module")
-def l1():
+def _l1_vectors():
     man = json.load(open(os.path.join(GOLDEN, "golden_l1.json")))
     blob = open(os.path.join(GOLDEN, "qlz_l1_vectors.bin"), "rb").read()
     get = lambda span: blob[span[0]:span[0] + span[1]]  # noqa: E731
     return [(v["name"], get(v["input"]), get(v["ref"])) for v in man["vectors"]]
+
+
+@pytest.fixture(scope="module")
+def l1():
+    return _l1_vectors()
 
 
 def _decode_batch(streams, caps):

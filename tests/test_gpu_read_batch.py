@@ -110,10 +110,14 @@ def _offsets(data: bytes):
     return [r.offset for r in recs]
 
 
-@pytest.fixture(scope="module")
-def rfile():
+def _rfile():
     data = _random_file(random.Random(7), 60)
     return data, _offsets(data)
+
+
+@pytest.fixture(scope="module")
+def rfile():
+    return _rfile()
 
 
 def test_golden_chunk(cuda, golden):

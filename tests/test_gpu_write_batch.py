@@ -123,9 +123,13 @@ def _run(keys, vals, flags=None, vers=None, ts=None, nc=record.NOT_COMPRESS, max
     return res, rows
 
 
+def _texts():
+    return {n: O.gen_text(2, n & 0xff, n) for n in (231, 232, 4096, 10240, 10241, 20000, 70000)}
+
+
 @pytest.fixture(scope="module")
 def texts():
-    return {n: O.gen_text(2, n & 0xff, n) for n in (231, 232, 4096, 10240, 10241, 20000, 70000)}
+    return _texts()
 
 
 def test_golden_records(cuda, golden):
@@ -286,8 +290,7 @@ def test_stored_block(cuda):
     assert len(rows[0][2]) == _pad256(24 + 1 + n) + 256 == rows[1][1]
 
 
-@pytest.mark.parametrize("n", [1, 64, 65, 257, 1100])
-def test_batch_shapes(cuda, n):
+def _shape_inputs(n):
     rng = random.Random(n)
     text = O.gen_text(7, 3, 1400)
     keys, vals, flags, vers = [], [], [], []
@@ -297,6 +300,12 @@ def test_batch_shapes(cuda, n):
         vals.append(text[o:o + ln])
         flags.append(rng.choice((0, 0, 0, FCC, 1)))
         vers.append(rng.randrange(-1, 5))
+    return keys, vals, flags, vers
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 257, 1100])
+def test_batch_shapes(cuda, n):
+    keys, vals, flags, vers = _shape_inputs(n)
     res, rows = _run(keys, vals, flags=flags, vers=vers, ts=list(range(n)), seed=n)
     assert all(r[0] == OK for r in rows)
 
