@@ -1,7 +1,9 @@
 // qlzx_api.hip -- the C ABI of libqlzx.so (declared in include/qlzx.h): the batch entry points'
 // argument checks and dispatch.  The whole-GPU drivers for values over 64 KiB sit with their
 // kernels (qlzx_decode_huge.hip, qlzx_encode_huge.hip), the batch decoder's launcher in
-// qlzx_decode_batch.hip, the single-call entry points in qlzx_single.hip.
+// qlzx_decode_batch.hip, the workgroup encoder's (launch_encode_wg, launch_encode_wg_class) in
+// qlzx_encode_wg.hip, the single-call entry points in qlzx_single.hip.  The three encoders take the
+// format's rules (hash, match token, bail-out test, header) from qlzx_encode_fmt.h.
 //
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
@@ -164,10 +166,7 @@ int qlzx_decompress_batch(const qlzx_blocks *b, const uint32_t *dst_cap, uint32_
 
 size_t qlzx_compress_workspace_size(uint32_t n, uint32_t max_len) {
     // at least one lane slab: QLZX_F_GO_COMPAT batches (flags are not known here) take the lane path
-    size_t ws = qlzx::kLaneSlab;
-    if (!qlzx::encode_wg_enabled())
-        ws = (size_t)std::min<uint32_t>(std::max<uint32_t>(n, 1), kMaxLaneSlabs) * qlzx::kLaneSlab;
-    ws = std::max(ws, qlzx::encode_wg_ws_bytes(n, max_len));
+    size_t ws = std::max(qlzx::kLaneSlab, qlzx::encode_wg_ws_bytes(n, max_len));
     if (max_len > QLZX_WG_MAX_LEN)  // values over 64 KiB: the pending list and the whole-GPU encoder
         ws += align_up((size_t)std::max<uint32_t>(n, 1) * sizeof(qlzx::HeItem) + 256, 256) +
               qlzx::he_ws_layout(max_len, nullptr, nullptr);
@@ -185,18 +184,18 @@ int qlzx_compress_batch(const qlzx_blocks *b, uint32_t *csize, int32_t *status,
                                 qlzx_compress_workspace_size(b->n, max_len)))
         return r;
     hipStream_t s = (hipStream_t)stream;
-    const bool wg = qlzx::encode_wg_enabled() && !(flags & QLZX_F_GO_COMPAT);
+    const bool wg = !(flags & QLZX_F_GO_COMPAT);
     const bool huge = max_len > QLZX_WG_MAX_LEN;  // values over 64 KiB: qlzx_encode_huge.hip
     if (wg) {
-        int r = qlzx::launch_encode_wg(*b, csize, status, crc_state, crc_out, max_len, flags, workspace, s);
+        int r = qlzx::launch_encode_wg(*b, csize, status, crc_state, crc_out, max_len, workspace, s);
         if (r) return fail(QLZX_R_HIP, "encode_wg launch", (hipError_t)r);
     }
-    if (!wg) {  // the lane encoder: Go-compat batches (and a disabled workgroup encoder) up to 64 KiB
+    if (!wg) {  // the lane encoder: Go-compat batches up to 64 KiB
         const uint32_t nl = (uint32_t)std::min<size_t>(
             std::min<uint32_t>(b->n, kMaxLaneSlabs), workspace_bytes / qlzx::kLaneSlab);
         if (nl == 0) return fail(QLZX_R_WORKSPACE, "qlzx_compress_batch: no lane slab");
         hipLaunchKernelGGL(qlzx::k_encode_lane, dim3((nl + 63) / 64), dim3(64), 0, s, *b, csize, status,
-                           crc_state, crc_out, (uint8_t *)workspace, nl, 0u, huge ? (uint32_t)QLZX_WG_MAX_LEN : 0u,
+                           crc_state, crc_out, (uint8_t *)workspace, nl, huge ? (uint32_t)QLZX_WG_MAX_LEN : 0u,
                            flags);
         HIP_OK(hipGetLastError());
     }

@@ -21,6 +21,7 @@
 // value.  Included after qlzx_decode_huge.hip (k_h_crcseg, read_pending).
 #include <rocprim/rocprim.hpp>
 
+#include "qlzx_encode_fmt.h"
 #include "qlzx_host.h"
 
 namespace qlzx {
@@ -43,8 +44,6 @@ __device__ __forceinline__ uint32_t he_ld32(const uint8_t *p) {  // unaligned, a
 }
 __device__ __forceinline__ uint32_t he_ld24(const uint8_t *p) { return he_ld32(p) & 0xffffffu; }
 
-// main-loop positions: ip <= n - 1 - QLZX_TAIL (quicklz.c:204,213)
-__host__ __device__ inline uint32_t he_positions(uint32_t n) { return n > QLZX_TAIL ? n - QLZX_TAIL : 0u; }
 __host__ inline uint32_t he_levels(uint32_t P) {
     uint32_t L = 1;
     while (L < kHeLevelsMax && (1ull << L) * 64 <= P) L++;
@@ -54,7 +53,7 @@ __host__ inline uint32_t he_levels(uint32_t P) {
 __global__ void __launch_bounds__(kHeWG) k_he_keys(const uint8_t *src, uint32_t P, uint16_t *key, uint32_t *pos) {
     for (uint32_t i = blockIdx.x * kHeWG + threadIdx.x; i < P; i += gridDim.x * kHeWG) {
         const uint32_t f = (uint32_t)src[i] | ((uint32_t)src[i + 1] << 8) | ((uint32_t)src[i + 2] << 16);
-        key[i] = (uint16_t)(((f >> 12) ^ f) & (QLZX_BUCKETS - 1));  // hash_func, quicklz.c:70
+        key[i] = (uint16_t)hash12(f);
         pos[i] = i;
     }
 }
@@ -145,21 +144,6 @@ __global__ void __launch_bounds__(kHeWG) k_he_expand(const uint32_t *Jk1, const 
     }
 }
 
-__device__ __forceinline__ uint32_t he_tok_bytes(uint32_t ml, uint32_t off) {  // quicklz.c:377-406
-    if (ml == 3 && off <= 63) return 1;
-    if (ml == 3 && off <= 16383) return 2;
-    if (ml <= 18 && off <= 1023) return 2;
-    if (ml <= 33) return 3;
-    return 4;
-}
-__device__ __forceinline__ uint32_t he_tok(uint32_t ml, uint32_t off) {
-    if (ml == 3 && off <= 63) return off << 2;
-    if (ml == 3 && off <= 16383) return (off << 2) | 1u;
-    if (ml <= 18 && off <= 1023) return ((ml - 3) << 2) | (off << 6) | 2u;
-    if (ml <= 33) return ((ml - 2) << 2) | (off << 7) | 3u;
-    return ((ml - 3) << 7) | (off << 15) | 3u;
-}
-
 // output bytes of every item (main-loop items, then the literal tail); sizes[ntot] = 0
 __global__ void __launch_bounds__(kHeWG) k_he_sizes(const uint32_t *ITEM, const uint32_t *MO, const HeCtl *ctl,
                                                     uint32_t ntot, uint32_t *sizes) {
@@ -168,7 +152,8 @@ __global__ void __launch_bounds__(kHeWG) k_he_sizes(const uint32_t *ITEM, const 
         uint32_t sz = t < ntot ? 1u : 0u;
         if (t < m) {
             const uint32_t mo = MO[ITEM[t]], ml = mo & 255u;
-            if (ml) sz = he_tok_bytes(ml, mo >> 8);
+            uint32_t v;
+            if (ml) sz = match_token(ml, mo >> 8, v);
         }
         sizes[t] = sz;
     }
@@ -181,7 +166,7 @@ __global__ void __launch_bounds__(kHeWG) k_he_bail(const uint32_t *ITEM, const u
     const uint32_t m = ctl->m;
     for (uint32_t g = 1 + blockIdx.x * kHeWG + threadIdx.x; 31u * g < m; g += gridDim.x * kHeWG) {
         const uint64_t ip = ITEM[31u * g], op = 4ull * g + S[31u * g];
-        if (ip > 3ull * (n >> 2) && op + bias > ip - (ip >> 5)) atomicOr(&ctl->bail, 1u);
+        if (bail_out(ip, op, n, bias)) atomicOr(&ctl->bail, 1u);
     }
 }
 
@@ -194,8 +179,9 @@ __global__ void __launch_bounds__(kHeWG) k_he_write(const uint8_t *src, const ui
         const uint32_t p = t < m ? ITEM[t] : tail0 + (t - m);
         const uint32_t mo = t < m ? MO[p] : 0u, ml = mo & 255u;
         if (ml) {
-            const uint32_t v = he_tok(ml, mo >> 8), nb = he_tok_bytes(ml, mo >> 8);
-            for (uint32_t b = 0; b < nb; b++) out[o + b] = (uint8_t)(v >> (8 * b));
+            uint32_t v;
+            const uint32_t nb = match_token(ml, mo >> 8, v);
+            put_token(out + o, v, nb);
         } else {
             out[o] = src[p];
         }
@@ -203,7 +189,7 @@ __global__ void __launch_bounds__(kHeWG) k_he_write(const uint8_t *src, const ui
             uint32_t cw = 0x80000000u;
             for (uint32_t j = 0; j < 31 && t + j < m; j++) cw |= ((MO[ITEM[t + j]] & 255u) ? 1u : 0u) << j;
             const uint32_t co = 4 * g + S[t];
-            for (uint32_t b = 0; b < 4; b++) out[co + b] = (uint8_t)(cw >> (8 * b));
+            st32(out + co, cw);
         }
     }
 }
@@ -214,9 +200,7 @@ __global__ void __launch_bounds__(kHeWG) k_he_copy(const uint8_t *s, uint8_t *d,
 __global__ void k_he_header(uint8_t *dst, bool compressed, uint32_t csize, uint32_t n, uint32_t *csize_out,
                             int32_t *status) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const uint32_t f = 2u | (compressed ? 1u : 0u) | 0x4Cu;  // long header, level 3 (quicklz.c:757-772)
-    dst[0] = (uint8_t)f;
-    for (uint32_t b = 0; b < 4; b++) dst[1 + b] = (uint8_t)(csize >> (8 * b)), dst[5 + b] = (uint8_t)(n >> (8 * b));
+    write_header(dst, 9, compressed, csize, n);  // the long header: n > 64 KiB >= 216
     *csize_out = csize;
     if (status) *status = QLZX_OK;
 }
@@ -243,7 +227,7 @@ struct HeWs {
     size_t tmp_bytes;
 };
 inline size_t he_ws_layout(uint32_t nmax, uint8_t *ws, HeWs *w) {
-    const uint32_t P = he_positions(nmax), L = he_levels(P);
+    const uint32_t P = searched_positions(nmax), L = he_levels(P);
     size_t sort_tmp = 0, scan_tmp = 0;
     (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (const uint16_t *)nullptr, (uint16_t *)nullptr,
                               (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)P, 0, 12);
@@ -307,7 +291,7 @@ inline int huge_encode_one(const uint8_t *src, uint32_t n, uint8_t *dst, uint32_
                            hipStream_t s) {
     HeWs w;
     he_ws_layout(nmax, ws, &w);
-    const uint32_t P = he_positions(n), L = he_levels(P);
+    const uint32_t P = searched_positions(n), L = he_levels(P);
     const dim3 G(kHeGrid), B(kHeWG);
     HIP_OK(hipMemsetAsync(w.ctl, 0, sizeof(HeCtl), s));
     hipLaunchKernelGGL(k_he_keys, G, B, 0, s, src, P, w.key, w.pos);

@@ -307,8 +307,7 @@ struct Service {
             hipLaunchKernelGGL(qlzx::k_svc_enc_in, dim3(n), dim3(256), 0, s, B[qlzx::kSvcCompress],
                                (const uint8_t *)h_arena, d_arena, desc);
             qlzx_blocks bl{d_arena, desc->src_off, desc->src_len, d_arena, desc->dst_off, n};
-            hipLaunchKernelGGL(qlzx::k_encode_wg<65536>, dim3(n), dim3(1024), 0, s, bl, desc->csize, desc->status,
-                               (const uint32_t *)nullptr, (uint32_t *)nullptr, ews, &desc->ticket);
+            qlzx::launch_encode_wg_class(65536, n, bl, desc->csize, desc->status, nullptr, nullptr, ews, &desc->ticket, s);
             hipLaunchKernelGGL(qlzx::k_svc_enc_out, dim3(n), dim3(256), 0, s, B[qlzx::kSvcCompress], h_arena,
                                (const uint8_t *)d_arena, (const qlzx::SvcEncDesc *)desc, h_done);
         }

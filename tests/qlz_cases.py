@@ -554,7 +554,7 @@ def huge_edges():
         out.append(_far(f"huge_edges/far{off}_nearer", off, nearer=True))
     for n in (65537, 65545, 65546, 65547, 131081, 131082):
         out.append(Case(f"huge_edges/text_n{n}", "huge_edges", text(9, n), {}))
-    for L, off in HUGE_PAIRS:                          # its own token table: he_tok_size, he_tok
+    for L, off in HUGE_PAIRS:                          # the shared token table (match_token), its own emission
         out.append(_pair(f"huge_edges/len{L}_off{off}", L, off, None, n=70000 + L, family="huge_edges"))
     out.append(_repeat300("huge_edges/repeat300", None, n=70300, family="huge_edges"))
     for r in (256, 257, 271, 272):

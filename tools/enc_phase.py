@@ -10,10 +10,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from gobeansdb_amd import _lib, batch  # noqa: E402
-sys.argv += [] if len(sys.argv) > 1 else []
-import importlib.util  # noqa: E402
-
-spec = importlib.util.spec_from_file_location("ep", os.path.join(os.path.dirname(__file__), "enc_prof.py"))
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 bs = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
 L = _lib.lib()
