@@ -3,7 +3,10 @@
 // kernels (qlzx_decode_huge.hip, qlzx_encode_huge.hip), the batch decoder's launcher in
 // qlzx_decode_batch.hip, the workgroup encoder's (launch_encode_wg, launch_encode_wg_class) in
 // qlzx_encode_wg.hip, the single-call entry points in qlzx_single.hip.  The three encoders take the
-// format's rules (hash, match token, bail-out test, header) from qlzx_encode_fmt.h.
+// format's rules (hash, match token, bail-out test, header) from qlzx_encode_fmt.h.  The
+// position-parallel decoders (qlzx_decode_solo.h and qlzx_decode_small.h, which hold no kernel and
+// run inside the request service's k_svc_decode, and qlzx_decode_huge.hip) take theirs from
+// qlzx_decode_fmt.h.
 //
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
@@ -22,8 +25,8 @@
 #include "qlzx_tables.hip"
 #include "qlzx_crc.hip"
 #include "qlzx_synth.hip"
-#include "qlzx_decode_solo.hip"
-#include "qlzx_decode_small.hip"
+#include "qlzx_decode_solo.h"
+#include "qlzx_decode_small.h"
 #include "qlzx_decode_batch.hip"
 #include "qlzx_decode_lane8.hip"
 #include "qlzx_decode_huge.hip"

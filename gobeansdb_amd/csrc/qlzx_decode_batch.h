@@ -8,7 +8,7 @@
 // and K2 k_dec_chunk4 (qlzx_decode_k2.h; one WAVE per block: items 64 at a time, output 256 bytes
 // at a time, every byte gathered from the position it copies; the record CRC is verified first
 // when asked for, store/datafile.go:161-168).  The block order and the launcher are in
-// qlzx_decode_batch.hip; the single-call decoders (qlzx_decode_solo.hip, qlzx_decode_small.hip)
+// qlzx_decode_batch.hip; the single-call decoders (qlzx_decode_solo.h, qlzx_decode_small.h)
 // use the same records and helpers.
 #pragma once
 #include "qlzx_device.h"

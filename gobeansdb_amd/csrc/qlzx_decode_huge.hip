@@ -25,7 +25,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "qlzx_decode_batch.h"
+#include "qlzx_decode_fmt.h"
 #include "qlzx_host.h"
 
 namespace qlzx {
@@ -36,7 +36,7 @@ constexpr uint32_t kHugeGrid = 2048, kHugeWG = 256;
 
 struct HugeCtl {
     uint32_t ngroups, nseg, klast, st;
-    uint32_t bad, done, tail_idx, max_match;
+    CheckAcc acc;
     uint32_t crc;
     uint32_t pad[7];
     uint32_t changed[64];  // pointer-jumping rounds
@@ -79,47 +79,19 @@ inline size_t huge_ws_layout(uint64_t m, uint8_t *base, HugeWs *w) {
     return o;
 }
 
-__device__ __forceinline__ uint32_t hg_ld32(const uint8_t *p) { return *(const uint32_t *)p; }  // unaligned mode
-__device__ __forceinline__ uint32_t hg_code(const uint32_t *code, uint32_t x) {
-    return __builtin_amdgcn_ubfe(code[x >> 4], 2 * (x & 15u), 2);
-}
-__device__ __forceinline__ uint32_t hg_tokcode(uint32_t b) {
-    const uint32_t ty = (b & 3u) + ((b & 127u) == 3u ? 1u : 0u);
-    return __builtin_amdgcn_ubfe(0x32110u, ty * 4, 4);
-}
-
 __global__ void __launch_bounds__(kHugeWG) k_h_codes(const uint8_t *src, uint32_t n, uint32_t *code) {
     for (uint32_t w = blockIdx.x * kHugeWG + threadIdx.x; w < (n + 15) / 16; w += gridDim.x * kHugeWG) {
-        uint32_t v = 0;
-        if (16 * w + 16 <= n) {
-            const uint32_t d0 = hg_ld32(src + 16 * w), d1 = hg_ld32(src + 16 * w + 4);
-            const uint32_t d2 = hg_ld32(src + 16 * w + 8), d3 = hg_ld32(src + 16 * w + 12);
-            const uint32_t d4[4] = {d0, d1, d2, d3};
-#pragma unroll
-            for (uint32_t j = 0; j < 16; j++) v |= hg_tokcode(d4[j >> 2] >> (8 * (j & 3))) << (2 * j);
-        } else {
-            for (uint32_t j = 0; j < 16 && 16 * w + j < n; j++) v |= hg_tokcode(src[16 * w + j]) << (2 * j);
-        }
-        code[w] = v;
+        const uint8_t *p = src + 16 * w;
+        code[w] = 16 * w + 16 <= n ? pack_codes16(ld_dword(p), ld_dword(p + 4), ld_dword(p + 8), ld_dword(p + 12))
+                                   : pack_codes_tail(p, n - 16 * w);
     }
 }
 
 __global__ void __launch_bounds__(kHugeWG) k_h_delta(const uint8_t *src, uint32_t n, uint32_t hdr, const uint32_t *code,
                                                   uint8_t *delta) {
     for (uint32_t x = blockIdx.x * kHugeWG + threadIdx.x; x < n + 256; x += gridDim.x * kHugeWG) {
-        uint32_t d = 0;
-        if (x >= hdr && x + 128 <= n) {
-            const uint32_t cw = hg_ld32(src + x);
-            if (cw >> 31) {  // C1
-                uint32_t mrem = cw & 0x7fffffffu, extra = 0;
-                while (mrem) {
-                    extra += hg_code(code, x + 4 + __builtin_ctz(mrem) + extra);
-                    mrem &= mrem - 1;
-                }
-                d = 35 + extra;
-            }
-        }
-        delta[x] = (uint8_t)d;
+        const bool in = x >= hdr && x + 128 <= n;  // no shortcut within 128 B of the end
+        delta[x] = (uint8_t)(in ? spec_group_len(ld_dword(src + x), CodeWords{code}, x) : 0u);
     }
 }
 
@@ -147,8 +119,7 @@ __global__ void __launch_bounds__(64) k_h_walk(const uint8_t *src, uint32_t n, u
     const uint32_t gmax = (uint32_t)huge_gmax(m);
     uint32_t x = hdr, g = 0, ns = 0, klast = 31;
     int st = QLZX_OK;
-    for (;;) {
-        if (x + 4 > n) break;  // the stream ends at a control word
+    while (x + 4 <= n) {  // else: the stream ends at a control word
         int k = (int)kHugeLevels;
         uint32_t j = 0;
         for (; k >= 1; k--) {
@@ -166,27 +137,16 @@ __global__ void __launch_bounds__(64) k_h_walk(const uint8_t *src, uint32_t n, u
         seg[ns++] = HugeSeg{x, g, 1, 0};
         g++;
         if (d) { x += d; continue; }
-        const uint32_t cw = hg_ld32(src + x);
-        if (!(cw >> 31)) { st = QLZX_E_CORRUPT; break; }  // C1
-        uint32_t p = x + 4, kk = 0;
-        for (; kk < 31 && p < n; kk++) {
-            const uint32_t c = ((cw >> kk) & 1u) ? hg_code(code, p) : 0u;
-            if (p + c + 1 > n) { st = QLZX_E_CORRUPT; break; }  // C2
-            p += c + 1;
-        }
-        if (st != QLZX_OK) break;
-        if (kk < 31) { klast = kk; break; }  // the stream ends inside this group
-        x = p;
+        uint32_t next = x;
+        st = parse_group_bytewise(ld_dword(src + x), x, n, CodeWords{code}, klast, next);
+        if (st != QLZX_OK || klast < 31) break;  // corrupt, or the stream ends inside this group
+        x = next;
     }
-    if (st == QLZX_OK && g == 0) st = QLZX_E_CORRUPT;
     ctl->ngroups = g;
     ctl->nseg = ns;
     ctl->klast = klast;
-    ctl->st = (uint32_t)st;
-    ctl->bad = 0;
-    ctl->done = 0;
-    ctl->tail_idx = 0xffffffffu;
-    ctl->max_match = 0;
+    ctl->st = (uint32_t)chain_status(st, g);
+    ctl->acc = check_acc_init();
 }
 
 __global__ void __launch_bounds__(kHugeWG) k_h_expand(const uint8_t *delta, const HugeSeg *seg, const HugeCtl *ctl,
@@ -206,11 +166,11 @@ __global__ void __launch_bounds__(kHugeWG) k_h_expand(const uint8_t *delta, cons
 template <typename F>
 __device__ __forceinline__ void hg_items(const uint8_t *src, uint32_t n, const uint32_t *code, uint32_t x, uint32_t nk,
                                          F &&f) {
-    const uint32_t cw = hg_ld32(src + x);
+    const uint32_t cw = ld_dword(src + x);
     uint32_t p = x + 4;
     for (uint32_t k = 0; k < nk; k++) {
         const bool ism = (cw >> k) & 1u;
-        const uint32_t t = p + 4 <= n ? hg_ld32(src + p) : (hg_ld32(src + n - 4) >> (8 * (p + 4 - n)));
+        const uint32_t t = p + 4 <= n ? ld_dword(src + p) : (ld_dword(src + n - 4) >> (8 * (p + 4 - n)));
         uint32_t off = 0, len = 1, tl = 1;
         if (ism) decode_tok_bf(t, off, len, tl);
         f(k, ism, t, p, tl, off, len);
@@ -232,7 +192,7 @@ __global__ void __launch_bounds__(kHugeWG) k_h_glen(const uint8_t *src, uint32_t
 
 // exclusive scan of glen (in place) by one workgroup of 1024 threads
 __global__ void __launch_bounds__(1024) k_h_scan(uint32_t *glen, const HugeCtl *ctl) {
-    __shared__ uint32_t wsum[16];
+    __shared__ uint32_t wsum[kBlockWaves];
     __shared__ uint32_t carry;
     if (ctl->st != QLZX_OK) return;
     const uint32_t ng = ctl->ngroups, tid = threadIdx.x;
@@ -266,39 +226,24 @@ __global__ void __launch_bounds__(kHugeWG) k_h_items(const uint8_t *src, uint32_
                                                   HugeCtl *ctl, uint32_t *sp, uint8_t *lit) {
     if (ctl->st != QLZX_OK) return;
     const uint32_t ng = ctl->ngroups, klast = ctl->klast;
-    const uint32_t tail_from = m > QLZX_TAIL ? m - 1 - QLZX_TAIL : 0;  // quicklz.c:503
-    uint32_t bad = 0, done = 0, tail_idx = 0xffffffffu, max_match = 0;
+    const uint32_t tail_from = tail_start(m);
+    CheckAcc acc = check_acc_init();
     for (uint32_t g = blockIdx.x * kHugeWG + threadIdx.x; g < ng; g += gridDim.x * kHugeWG) {
         uint32_t d = gd[g];
         hg_items(src, n, code, glist[g], g + 1 == ng ? klast : 31u,
                  [&](uint32_t k, bool ism, uint32_t t, uint32_t pos, uint32_t tl, uint32_t off, uint32_t len) {
-                     const uint32_t I = g * 31 + k;
-                     if (d < m) {
+                     if (d < m && check_item(ism, off, len, tl, pos, d, g * 31 + k, m, n, hdr, tail_from, acc)) {
                          if (ism) {
-                             max_match = max(max_match, I);
-                             if (off < 3 || off > d || (uint64_t)d + len + 4 > m) {
-                                 bad = 1;  // C3 (and no match within the last 4 bytes)
-                             } else {
-                                 for (uint32_t j = 0; j < len; j++) sp[d + j] = d + j - off;
-                             }
+                             for (uint32_t j = 0; j < len; j++) sp[d + j] = d + j - off;
                          } else {
                              sp[d] = d;
                              lit[d] = (uint8_t)t;
-                             if (d >= tail_from) tail_idx = min(tail_idx, I);
-                         }
-                         if ((uint64_t)d + len == m) {  // C5: the item completing dsize ends the stream
-                             done = 1;
-                             const uint32_t ip_end = pos + tl;
-                             if (!(ip_end == n || (ip_end < hdr + 9 && n == hdr + 9))) bad = 1;
                          }
                      }
                      d += len;
                  });
     }
-    if (bad) atomicOr(&ctl->bad, 1u);
-    if (done) atomicOr(&ctl->done, 1u);
-    if (tail_idx != 0xffffffffu) atomicMin(&ctl->tail_idx, tail_idx);
-    if (max_match) atomicMax(&ctl->max_match, max_match);
+    check_acc_merge(&ctl->acc, acc);
 }
 
 // s[p] <- s[s[p]]; a stale read is an earlier link of the same chain, so it costs only a round
@@ -454,8 +399,7 @@ inline int huge_one(const uint8_t *src, uint32_t csize, uint8_t *dst, uint32_t d
     HIP_OK(hipMemcpyAsync(&h, w.ctl, sizeof(HugeCtl), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     if (h.st == QLZX_E_CRC) return QLZX_R_OK;  // already reported
-    const bool corrupt = h.st != QLZX_OK || h.bad || !h.done || (h.tail_idx != 0xffffffffu && h.max_match > h.tail_idx);
-    if (corrupt) {
+    if (h.st != QLZX_OK || verdict_corrupt(h.acc)) {
         hipLaunchKernelGGL(k_h_setstatus, dim3(1), dim3(64), 0, s, status, dsize_out, (int32_t)QLZX_E_CORRUPT, 0u);
         HIP_OK(hipGetLastError());
         return QLZX_R_OK;

@@ -41,6 +41,8 @@ constexpr size_t kSvcRecs = ((size_t)kSoloGmax * sizeof(GroupRec) + 255) & ~(siz
 static_assert(kSoloGmax * sizeof(GroupRec) <= (1u << 20), "solo records");
 constexpr size_t kSvcDevSlot = kSvcIn + kSvcOut + kSvcRecs;
 static_assert(kSvcIn >= kSoloMaxCsize + 64 && kSvcOut >= kSvcMaxLen + 400 + 64, "slot sizes");
+// solo_decode's precondition: the slot's src (its start) and dst (kSvcIn on) are 16-B aligned
+static_assert(kSvcIn % 16 == 0 && kSvcHostSlot % 16 == 0 && kSvcDevSlot % 16 == 0, "16-B aligned slots");
 
 enum : uint32_t { kSvcDecode = 0, kSvcCompress = 1, kSvcCrc = 2, kSvcOps = 3 };
 
@@ -117,13 +119,12 @@ __global__ void __launch_bounds__(kSoloWG) k_svc_decode(SvcBatch B, const uint8_
         svc_publish(done, r, st == QLZX_OK ? ds : 0u, st, crc);
         return;
     }
-    SoloLds &L = U.solo;
     uint8_t *dsrc = d_arena + (size_t)r.slot * kSvcDevSlot, *ddst = dsrc + kSvcIn;
     const uint32_t tid = threadIdx.x;
     svc_copy(dsrc, hin, r.len, tid, kSoloWG);
     __threadfence();
     __syncthreads();
-    solo_decode(L, dsrc, r.len, ddst, r.cap, r.cap, (GroupRec *)(ddst + kSvcOut), &st, &ds);
+    solo_decode(U.solo, dsrc, r.len, ddst, r.cap, r.cap, (GroupRec *)(ddst + kSvcOut), &st, &ds);
     __threadfence();
     __syncthreads();
     const uint32_t n = st == QLZX_OK ? ds : 0u;

@@ -1,7 +1,7 @@
 """GPU parity of the single-call latency path: qlz_decompress on one block (dsize <= 64 KiB,
 csize <= 64 KiB) is one request to the service, whose k_svc_decode runs the workgroup-parallel
-parse and decode (small_decode, csrc/qlzx_decode_small.hip, or solo_decode,
-csrc/qlzx_decode_solo.hip).  Bytes and statuses must equal the oracle's (oracle/qlz_oracle.c,
+parse and decode (small_decode, csrc/qlzx_decode_small.h, or solo_decode,
+csrc/qlzx_decode_solo.h).  Bytes and statuses must equal the oracle's (oracle/qlz_oracle.c,
 pinned to quicklz.c by the golden vectors) on valid, corrupted and truncated streams."""
 import ctypes
 

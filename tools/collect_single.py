@@ -24,7 +24,7 @@ p50_bar, agg_bar = (35, 8.0) if rnd >= 5 else (30, None)
 res = {
     "what": "single-call drop-ins (qlz_decompress / qlz_compress / crc32_write) on one MI355X: per-call "
             "latency (one caller), aggregate qlz_decompress of 1 and 16 pthreads (tools/mt_single.c), and the "
-            "small-block decoder's phase stamps (core cycles, qlzx_decode_small.hip); every call on the next of "
+            "small-block decoder's phase stamps (core cycles, qlzx_decode_small.h); every call on the next of "
             "1024 distinct values per size, on both sides",
     "command": "tools/gpu_r5s.sh" if rnd >= 5 else "tools/gpu_r4j.sh + tools/gpu_r4c.sh",
     "latency": lat,

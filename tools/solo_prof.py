@@ -1,5 +1,5 @@
-"""Phase stamps of the single-call latency decoders (solo_decode, csrc/qlzx_decode_solo.hip, and
-small_decode, csrc/qlzx_decode_small.hip, inside the request service's k_svc_decode) from the
+"""Phase stamps of the single-call latency decoders (solo_decode, csrc/qlzx_decode_solo.h, and
+small_decode, csrc/qlzx_decode_small.h, inside the request service's k_svc_decode) from the
 -DQLZX_PROFILE build, plus the host-side split of one qlz_decompress call.
 
 usage: QLZX_LIB=gobeansdb_amd/libqlzx_prof.so python tools/solo_prof.py [calls]
@@ -37,7 +37,7 @@ for n in (4096, 16384, 32768, 65536):
         L.qlz_decompress(c, out, None)
         ts.append(time.perf_counter_ns() - t0)
     p = prof.cpu().numpy().astype(np.float64)
-    if p[31] > 0:  # the small-block LDS path (qlzx_decode_small.hip) took the calls
+    if p[31] > 0:  # the small-block LDS path (qlzx_decode_small.h) took the calls
         k = p[31]
         ph = {nm: round(p[24 + j] / k) for j, nm in enumerate(names_small)}
         ph["(stage)"] = round(p[16] / k)
