@@ -11,8 +11,8 @@
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
 // (replay, read, write, gc, hint) share qlzx_recfile.h; read also uses replay's k_rp_crc_long,
-// ScatterComp and finish kernels, qlzx_hintmerge.hip uses qlzx_hint.hip's sort, run, index and
-// file kernels, and qlzx_hintlookup.hip its key hash and qlzx_hintmerge.hip's loads.
+// ScatterComp and finish kernels.  The three hint sources (hint, hintmerge, hintlookup) share
+// qlzx_hint_fmt.h, which each includes itself: their order here does not matter.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

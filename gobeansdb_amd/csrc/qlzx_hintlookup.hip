@@ -13,7 +13,10 @@
 //          head or key that runs past the file is the error, decided before the item is compared.
 //          QLZX_HL_F_BOUNDED stops at indexOffset.
 //
-// Launches: k_keyhash (qlzx_hint.hip) into the workspace unless the caller brings
+// The format with its loads, the reader's rule (hint_next) and k_keyhash are qlzx_hint_fmt.h's;
+// this file owns the head check, hl_start, hl_step, the LDS window and the two kernel shapes.
+//
+// Launches: k_keyhash into the workspace unless the caller brings
 // hashes; k_hl_head, one lane per file: the head's checks, once; then one of two shapes of the
 // same search, hl_start and the item loop being the same code over a different byte source:
 //   k_hl_wave  a wave per request, below QLZX_HL_LANE_FROM requests.  The stretch is staged in LDS
@@ -27,11 +30,12 @@
 // and the chip holds 8,192 waves but 524,288 lanes: the wave shape is 2-3 times faster while its
 // requests fit the chip at once, the lane shape 4-5 times faster at 262,144 requests
 // (profiles/r14_hint_lookup.json).
-#include "qlzx_recfile.h"
+#include "qlzx_hint_fmt.h"
 
 namespace qlzx {
 
 constexpr uint32_t kHlWin = 4096;                          // bytes of one LDS window (a multiple of 16)
+constexpr uint32_t kHlHold = kHlWin - 16;                  // of which file bytes: byte 22 behind any of them is in the slice
 constexpr uint32_t kHlItemMax = kHintItem + kHintMaxKey;   // the longest item
 
 struct HlIn {
@@ -70,9 +74,9 @@ __global__ void __launch_bounds__(256) k_hl_head(HlIn in, HlFile *files) {
         HlFile s{in.file_off[i], in.file_len[i], 0, 0, in.file_chunk[i], in.file_flags[i] & QLZX_HL_FILE_MERGED, 0, 0};
         s.bad = s.len < kHintHead || s.off > in.bytes || in.bytes - s.off < s.len;
         if (!s.bad) {
-            s.io = hm_ld64(in.hints + s.off);
-            if (s.io < kHintHead || s.io > s.len || (s.len - s.io) % 16 != 0) s.bad = 1;
-            else s.ne = (s.len - s.io) / 16;
+            s.io = hint_ld64(in.hints + s.off);
+            if (s.io < kHintHead || s.io > s.len || (s.len - s.io) % kHintEntry != 0) s.bad = 1;
+            else s.ne = (s.len - s.io) / kHintEntry;
         }
         files[i] = s;
     }
@@ -85,12 +89,12 @@ __device__ __forceinline__ bool hl_start(const uint8_t *f, const HlFile &s, uint
     uint64_t i = 0, j = s.ne;
     while (i < j) {
         const uint64_t h = (i + j) >> 1;
-        if (!(hm_ld64(f + s.io + 16 * h) >= kh)) i = h + 1;
+        if (!(hint_ld64(f + s.io + kHintEntry * h) >= kh)) i = h + 1;
         else j = h;
     }
     *start = kHintHead;
     if (i > 1) {
-        *start = hm_ld64(f + s.io + 16 * (i - 1) + 8);
+        *start = hint_ld64(f + s.io + kHintEntry * (i - 1) + kEntryOffset);
         if (*start < kHintHead || *start > s.len) return false;
     }
     *stop = bounded ? s.io : s.io + (*start - kHintHead);
@@ -109,11 +113,10 @@ __device__ __forceinline__ int32_t hl_get_lane(const uint8_t *f, const HlFile &s
                                                uint32_t klen, bool bounded, uint64_t *at) {
     uint64_t p, stop;
     if (!hl_start(f, s, kh, bounded, &p, &stop)) return QLZX_HL_ERR;
-    while (p < stop) {  // every step advances 23 bytes or more and p <= len
-        if (s.len - p < kHintItem) return QLZX_HL_ERR;
-        const uint32_t ksz = f[p + 22];
-        if (s.len - p - kHintItem < ksz) return QLZX_HL_ERR;
-        const int t = hl_step(hm_ld64(f + p), ksz, kh, klen);
+    while (p < stop) {  // p <= len
+        uint32_t ksz;
+        if (!hint_next(s.len, p, [&](uint64_t q) { return f[q]; }, &ksz)) return QLZX_HL_ERR;
+        const int t = hl_step(hint_ld64(f + p), ksz, kh, klen);
         if (t == kHlMiss) return QLZX_HL_MISS;
         if (t == kHlCandidate) {
             uint32_t d = 0;
@@ -142,11 +145,11 @@ struct HlWin {
         return __builtin_amdgcn_alignbyte(lds[(o >> 2) + 1], lds[o >> 2], o & 3u);
     }
     __device__ __forceinline__ uint64_t ld64(uint64_t q) const { return ld32(q) | ((uint64_t)ld32(q + 4) << 32); }
-    // file bytes [p, min(len, end, p + kHlWin - sh)); the wave's earlier reads of the window are done
+    // file bytes [p, min(len, end, p + kHlHold - sh)); the wave's earlier reads of the window are done
     __device__ __forceinline__ void stage(const uint8_t *f, uint64_t len, uint64_t p, uint64_t end, uint32_t lane) {
         sh = (uint32_t)((uintptr_t)(f + p) & 15u);
         w0 = p;
-        w1 = len - p < kHlWin - sh ? len : p + (kHlWin - sh);
+        w1 = len - p < kHlHold - sh ? len : p + (kHlHold - sh);
         if (end < w1) w1 = end;
         const uint32_t chunks = (sh + (uint32_t)(w1 - w0) + 15) / 16;
         for (uint32_t c = lane; c < chunks; c += 64) {
@@ -179,14 +182,17 @@ __device__ __forceinline__ int32_t hl_get_wave(const uint8_t *f, const HlFile &s
     const uint64_t end = stop >= s.len || s.len - stop < kHlItemMax ? s.len : stop + kHlItemMax;
     w.w0 = w.w1 = 0;
     while (p < stop) {
-        if (s.len - p < kHintItem) return QLZX_HL_ERR;
         // the window holds the item whole, whatever its ksz, or reaches `end`
         if (w.w1 <= p || (w.w1 < end && w.w1 - p < kHlItemMax)) {
             __builtin_amdgcn_wave_barrier();
             w.stage(f, s.len, p, end, lane);
         }
-        const uint32_t ksz = w.byte(p + 22);
-        if (s.len - p - kHintItem < ksz) return QLZX_HL_ERR;
+        // The ksz byte is read before the rule asks for it: read between the rule's two checks it costs
+        // the loop 70 instructions and 20-30 % (profiles/r15_hint_kernels_ab.txt).  Under a head that
+        // the file cuts it is a byte of the slice past the window (kHlHold) and is not used.
+        const uint32_t kb = w.byte(p + kItemKsz);
+        uint32_t ksz;
+        if (!hint_next(s.len, p, [&](uint64_t) { return kb; }, &ksz)) return QLZX_HL_ERR;
         const int t = hl_step(w.ld64(p), ksz, kh, klen);
         if (t == kHlMiss) return QLZX_HL_MISS;
         if (t == kHlCandidate) {
@@ -224,32 +230,39 @@ __device__ __forceinline__ void hl_report(const HlIn &in, const HlOut &out, cons
     if (h.status == QLZX_HL_FOUND) {
         const HlFile &s = files[h.file];
         const uint8_t *p = in.hints + s.off + h.at;
-        chunk = s.merged ? hm_ld32(p + 8) : s.chunk;
-        offset = hm_ld32(p + 12), ver = hm_ld32(p + 16), vhash = (uint32_t)p[20] | ((uint32_t)p[21] << 8);
+        chunk = s.merged ? hint_ld32(p + kItemChunk) : s.chunk;
+        offset = hint_ld32(p + kItemOffset), ver = hint_ld32(p + kItemVer);
+        vhash = (uint32_t)p[kItemVhash] | ((uint32_t)p[kItemVhash + 1] << 8);
         src = s.off + h.at;
     }
     out.status[r] = h.status, out.hit_file[r] = h.file;
     out.chunk[r] = chunk, out.offset[r] = offset, out.ver[r] = (int32_t)ver, out.vhash[r] = (uint16_t)vhash;
     out.item_src[r] = src;
 }
-// totals = {found, miss, err, bad_file}
-__device__ __forceinline__ uint32_t hl_slot(int32_t status) {
-    return status == QLZX_HL_FOUND ? 0u : status == QLZX_HL_MISS ? 1u : (uint32_t)status;
+// totals = {found, miss, err, bad_file}: one more in status's slot
+__device__ __forceinline__ void hl_count(uint32_t (&cnt)[4], int32_t status) {
+    const uint32_t slot = status == QLZX_HL_FOUND ? 0u : status == QLZX_HL_MISS ? 1u : (uint32_t)status;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) cnt[k] += slot == k;
 }
+// request r: its keyhash and key
+struct HlReq {
+    uint64_t kh;
+    const uint8_t *key;
+    uint32_t klen;
+    __device__ __forceinline__ HlReq(const HlIn &in, const uint64_t *hash, uint32_t r)
+        : kh(hash[r]), key(in.keys + in.key_off[r]), klen(in.key_len[r]) {}
+};
 
 __global__ void __launch_bounds__(256) k_hl_lane(HlIn in, const HlFile *files, const uint64_t *hash, HlOut out) {
     uint32_t cnt[4] = {0, 0, 0, 0};
     for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < in.n; r += gridDim.x * 256) {
-        const uint64_t kh = hash[r];
-        const uint8_t *key = in.keys + in.key_off[r];
-        const uint32_t klen = in.key_len[r];
+        const HlReq q(in, hash, r);
         const HlHit h = hl_files(in, files, [&](const uint8_t *f, const HlFile &s, uint64_t *at) {
-            return hl_get_lane(f, s, kh, key, klen, in.bounded, at);
+            return hl_get_lane(f, s, q.kh, q.key, q.klen, in.bounded, at);
         });
         hl_report(in, out, files, r, h);
-        const uint32_t slot = hl_slot(h.status);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) cnt[k] += slot == k;
+        hl_count(cnt, h.status);
     }
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) {
@@ -266,16 +279,12 @@ __global__ void __launch_bounds__(256) k_hl_wave(HlIn in, const HlFile *files, c
     w.lds = lds[wv];
     uint32_t cnt[4] = {0, 0, 0, 0};
     for (uint32_t r = blockIdx.x * 4 + wv; r < in.n; r += gridDim.x * 4) {
-        const uint64_t kh = hash[r];
-        const uint8_t *key = in.keys + in.key_off[r];
-        const uint32_t klen = in.key_len[r];
+        const HlReq q(in, hash, r);
         const HlHit h = hl_files(in, files, [&](const uint8_t *f, const HlFile &s, uint64_t *at) {
-            return hl_get_wave(f, s, kh, key, klen, in.bounded, w, lane, at);
+            return hl_get_wave(f, s, q.kh, q.key, q.klen, in.bounded, w, lane, at);
         });
         if (lane == 0) hl_report(in, out, files, r, h);
-        const uint32_t slot = hl_slot(h.status);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) cnt[k] += slot == k;
+        hl_count(cnt, h.status);
     }
     if (lane == 0)
         for (uint32_t k = 0; k < 4; k++)

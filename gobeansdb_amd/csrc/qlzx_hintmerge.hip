@@ -7,8 +7,12 @@
 // is: one item per distinct (keyhash, key), the one with the largest CmpKey, in (keyhash, key)
 // order.  A source that does not ascend is refused.
 //
-// Two calls, nothing read back in between; the sort, the run / fix kernels, the
-// (bytes, items) scan, the index walk and the file writer are qlzx_hint.hip's.
+// The format with its loads and the reader's rule (hint_next), the sort's workspace tail, the
+// run / fix kernels, the index pass and the file writer are qlzx_hint_fmt.h's; this file owns the
+// source heads, stretches and walks, the two sort keys, the collision flags, winners, emit and
+// totals, the writer's source of items (HmFile), the workspace layout and the two launchers.
+//
+// Two calls, nothing read back in between:
 //   plan   k_hm_head: every source's head.  The item starts of a source are a serial chain (ksz
 //          sits at byte 22 of an item), so a source is cut into stretches at the entries of its own
 //          sparse index, one lane per stretch: k_hm_count walks a stretch and must land exactly on
@@ -20,7 +24,7 @@
 //          Then the item numbers are sorted by CmpKey and, stably, by keyhash: a run of equal hash
 //          is in position order and k_hint_runs / k_hint_fix's "last of its group wins" applies.
 //   write  k_hint_file over HmFile: an item's 23 bytes come from its source with the chunk replaced.
-#include "qlzx_recfile.h"
+#include "qlzx_hint_fmt.h"
 
 namespace qlzx {
 
@@ -41,13 +45,6 @@ struct HmCounters {
     uint32_t status, fin, src, ncoll;  // status: after k_hm_fill; fin: the plan's verdict
 };
 
-__device__ __forceinline__ uint32_t hm_ld32(const uint8_t *p) {
-    uint32_t w;
-    __builtin_memcpy(&w, p, 4);
-    return w;
-}
-__device__ __forceinline__ uint64_t hm_ld64(const uint8_t *p) { return hm_ld32(p) | ((uint64_t)hm_ld32(p + 4) << 32); }
-
 // hintFileReader.open (store/hintfile.go:57-87).  A source that cannot yield an item is bad.
 __global__ void __launch_bounds__(256) k_hm_head(HmIn in, HmSrc *src, uint32_t *unproven, HintAcc *sv,
                                                  HintCounters *cnt, HmCounters *hm) {
@@ -56,8 +53,8 @@ __global__ void __launch_bounds__(256) k_hm_head(HmIn in, HmSrc *src, uint32_t *
         s.bad = s.len < kHintHead || s.off > in.bytes || in.bytes - s.off < s.len;
         if (!s.bad) {
             const uint8_t *f = in.hints + s.off;
-            const int64_t ix = (int64_t)hm_ld64(f);
-            atomicMax(&cnt->datasize, hm_ld32(f + 12));
+            const int64_t ix = (int64_t)hint_ld64(f);
+            atomicMax(&cnt->datasize, hint_ld32(f + kHeadDatasize));
             if (ix < 0 || (uint64_t)ix > s.len) {
                 s.bad = 1;
             } else if (ix == 0) {
@@ -65,7 +62,7 @@ __global__ void __launch_bounds__(256) k_hm_head(HmIn in, HmSrc *src, uint32_t *
             } else {
                 s.io = (uint64_t)ix;
                 // more entries than items fit below indexOffset, or than cap: no proof can hold
-                const uint64_t ne = (s.len - s.io) / 16;
+                const uint64_t ne = (s.len - s.io) / kHintEntry;
                 if (s.io > kHintHead && ne <= (s.io - kHintHead) / kHintItem && ne <= in.cap) s.ne = (uint32_t)ne;
             }
             if (s.io <= kHintHead) s.bad = 1;  // no item: merge dereferences a nil first item
@@ -105,17 +102,16 @@ struct HmStr {
     }
 };
 
-// hintFileReader.next from p while p < stop: emit(j, p) per item; false when an item's head or key
-// runs past the file.  Every step advances 23 bytes or more and p < stop <= len: the loop ends.
+// hintFileReader.next from p while p < stop <= len: emit(j, p) per item; false when an item's head
+// or key runs past the file.
 template <class E>
 __device__ __forceinline__ bool hm_walk(const uint8_t *f, uint64_t len, uint64_t *p_io, uint64_t stop, uint64_t *n,
                                         E emit) {
     uint64_t p = *p_io, j = 0;
     bool ok = true;
     while (p < stop) {
-        if (len - p < kHintItem) { ok = false; break; }
-        const uint32_t ksz = f[p + 22];
-        if (len - p - kHintItem < ksz) { ok = false; break; }
+        uint32_t ksz;
+        if (!hint_next(len, p, [&](uint64_t q) { return f[q]; }, &ksz)) { ok = false; break; }
         emit(j, p);
         p += kHintItem + ksz;
         j++;
@@ -129,8 +125,8 @@ __device__ __forceinline__ bool hm_walk(const uint8_t *f, uint64_t len, uint64_t
 // reads as a large one and fails.
 __device__ __forceinline__ bool hm_stretch(const uint8_t *f, const HmSrc &s, uint32_t m, uint64_t *start,
                                            uint64_t *stop) {
-    *start = m == 0 ? kHintHead : hm_ld64(f + s.io + 16ull * (m - 1) + 8);
-    *stop = m == s.ne ? s.io : hm_ld64(f + s.io + 16ull * m + 8);
+    *start = m == 0 ? kHintHead : hint_ld64(f + s.io + (uint64_t)kHintEntry * (m - 1) + kEntryOffset);
+    *stop = m == s.ne ? s.io : hint_ld64(f + s.io + (uint64_t)kHintEntry * m + kEntryOffset);
     if (*start < kHintHead || *start >= s.io || *stop > s.io) return false;
     if (m < s.ne && *stop >= s.io) return false;
     return m == 0 ? *start <= *stop : *start < *stop;
@@ -224,7 +220,7 @@ struct HmKey {
         if (r >= cap) return 0;
         const uint8_t *p = hints + pos[r];
         *k = p + kHintItem;
-        return p[22];
+        return p[kItemKsz];
     }
 };
 
@@ -235,7 +231,7 @@ __global__ void __launch_bounds__(256) k_hm_sorted(HmKey K, const uint32_t *sid,
     const uint32_t N = (uint32_t)hm->n;
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x + 1; k < N; k += gridDim.x * 256) {
         if (sid[k] != sid[k - 1]) continue;
-        const uint64_t ha = hm_ld64(K.hints + K.pos[k - 1]), hb = hm_ld64(K.hints + K.pos[k]);
+        const uint64_t ha = hint_ld64(K.hints + K.pos[k - 1]), hb = hint_ld64(K.hints + K.pos[k]);
         bool asc = ha < hb;
         if (ha == hb) {
             const uint8_t *a, *b;
@@ -257,7 +253,7 @@ __global__ void __launch_bounds__(256) k_hm_cmpkey(HmIn in, const uint64_t *pos,
     }
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < in.cap; k += gridDim.x * 256) {
         const bool v = k < nv;
-        key_in[k] = v ? ((uint64_t)in.file_chunk[sid[k]] << 32) | hm_ld32(in.hints + pos[k] + 12) : ~0ull;
+        key_in[k] = v ? ((uint64_t)in.file_chunk[sid[k]] << 32) | hint_ld32(in.hints + pos[k] + kItemOffset) : ~0ull;
         val_in[k] = v ? k : 0xffffffffu;
     }
 }
@@ -266,7 +262,7 @@ __global__ void __launch_bounds__(256) k_hm_hashkey(HmIn in, const uint64_t *pos
     const uint32_t nv = cnt->nv;
     for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < in.cap; j += gridDim.x * 256) {
         const uint32_t r = val_s[j];
-        key_in[j] = j < nv && r < in.cap ? hm_ld64(in.hints + pos[r]) : ~0ull;
+        key_in[j] = j < nv && r < in.cap ? hint_ld64(in.hints + pos[r]) : ~0ull;
     }
 }
 // cf[i] = a second or later key of its keyhash starts at sorted position i (mergeWriter.write's
@@ -332,7 +328,7 @@ __global__ void __launch_bounds__(256) k_hm_emit(HmIn in, const uint64_t *pos, c
 __global__ void k_hm_totals(uint32_t *totals, const HintCounters *cnt, const HmCounters *hm) {
     const bool ok = hm->fin == QLZX_HM_OK;
     const uint32_t nk = ok ? cnt->nk : 0u, nidx = ok ? cnt->nidx : 0u;
-    const uint64_t io = kHintHead + (ok ? cnt->ibytes : 0ull), fb = nk ? io + 16ull * nidx : 0;
+    const uint64_t io = kHintHead + (ok ? cnt->ibytes : 0ull), fb = nk ? io + (uint64_t)kHintEntry * nidx : 0;
     totals[0] = (uint32_t)(hm->n < 0xffffffffull ? hm->n : 0xffffffffull);
     totals[1] = nk, totals[2] = nidx, totals[3] = cnt->datasize;
     totals[4] = (uint32_t)io, totals[5] = (uint32_t)(io >> 32);
@@ -356,43 +352,30 @@ struct HmFile {
         const uint64_t o = item_src[k];
         return o <= bytes && bytes - o >= kHintItem ? hints + o : nullptr;
     }
+    __device__ __forceinline__ uint64_t keyhash(uint32_t k) const {
+        const uint8_t *p = item(k);
+        return p ? hint_ld64(p) : 0;
+    }
+    // the source's 23 bytes with the chunk replaced; the key only when it lies inside `hints`
+    __device__ __forceinline__ void head(uint32_t k, HintCur &c) const {
+        c.h2 = item_chunk[k];
+        if (const uint8_t *p = item(k)) {
+            c.h0 = hint_ld32(p), c.h1 = hint_ld32(p + 4), c.h3 = hint_ld32(p + kItemOffset), c.h4 = hint_ld32(p + kItemVer);
+            c.h5 = (uint32_t)p[kItemVhash] | ((uint32_t)p[kItemVhash + 1] << 8) | ((uint32_t)p[kItemKsz] << 16);
+            if (bytes - (uint64_t)(p - hints) - kHintItem >= p[kItemKsz]) c.ksz = p[kItemKsz], c.key = p + kHintItem;
+        }
+    }
 };
-__device__ __forceinline__ void hint_cur_load(const HmFile &f, const HintTot &t, uint32_t k, HintCur &c) {
-    c.k = k;
-    c.o = f.item_off[k];
-    c.next = k + 1 < t.nk ? f.item_off[k + 1] : t.io;
-    c.ksz = 0, c.key = nullptr;
-    c.h0 = 0, c.h1 = 0, c.h2 = f.item_chunk[k], c.h3 = 0, c.h4 = 0, c.h5 = 0;
-    if (const uint8_t *p = f.item(k)) {
-        c.h0 = hm_ld32(p), c.h1 = hm_ld32(p + 4), c.h3 = hm_ld32(p + 12), c.h4 = hm_ld32(p + 16);
-        c.h5 = (uint32_t)p[20] | ((uint32_t)p[21] << 8) | ((uint32_t)p[22] << 16);
-        if (f.bytes - (uint64_t)(p - f.hints) - kHintItem >= p[22]) c.ksz = p[22], c.key = p + kHintItem;
-    }
-}
-__device__ __forceinline__ uint32_t hint_index_dword(const HmFile &f, const HintTot &t, uint64_t d) {
-    if (d >= t.fb - t.io) return 0;
-    const uint32_t k = f.index_item[d >> 4], r = (uint32_t)d & 15u;
-    uint64_t x = 0;
-    if (k < t.nk) {
-        const uint8_t *p = f.item(k);
-        x = r >= 8 ? f.item_off[k] : p ? hm_ld64(p) : 0;
-    }
-    return (uint32_t)(x >> (8 * (r & 4)));
-}
 
-// ---- workspace ----
-struct HmWs {
+// ---- workspace: the counters, the sources, the stretches, the items' positions, the sort's tail ----
+struct HmWs : HintSortWs {
     HintCounters *cnt;
     HmCounters *hm;
     HmSrc *src;
-    uint32_t *unproven;
-    HintAcc *sv, *sb;        // the sources' stretch counts and their scan
-    HintAcc *a, *b;          // stretch counts and their scan; then key_in (a's second half) and itemv / items
-    uint64_t *key_in, *key_s, *pos;
-    uint32_t *val_in, *val_s, *val_r, *list, *fa, *fb, *sid;
-    uint8_t *fl, *gh;
-    void *tmp;
-    size_t tmp_bytes;
+    uint32_t *unproven, *sid;
+    HintAcc *sv, *sb;  // the sources' stretch counts and their scan
+    HintAcc *a, *b;    // stretch counts and their scan; then key_in (a's second half) and itemv / items
+    uint64_t *pos;
 };
 inline size_t hm_ws_layout(uint32_t n_files, uint32_t cap, uint8_t *base, HmWs *w) {
     const size_t m = (size_t)cap + 2, sm = (size_t)cap + n_files + 2;
@@ -406,20 +389,9 @@ inline size_t hm_ws_layout(uint32_t n_files, uint32_t cap, uint8_t *base, HmWs *
     t.sb = c.take<HintAcc>(16 * (size_t)n_files);
     t.a = c.take<HintAcc>(16 * sm);
     t.b = c.take<HintAcc>(16 * sm);
-    t.key_in = t.a ? (uint64_t *)t.a + m : nullptr;
-    t.key_s = c.take<uint64_t>(8 * m);
     t.pos = c.take<uint64_t>(8 * m);
-    t.val_in = c.take<uint32_t>(4 * m);
-    t.val_s = c.take<uint32_t>(4 * m);
-    t.val_r = c.take<uint32_t>(4 * m);
-    t.list = c.take<uint32_t>(4 * m);
-    t.fa = c.take<uint32_t>(4 * m);
-    t.fb = c.take<uint32_t>(4 * m);
     t.sid = c.take<uint32_t>(4 * m);
-    t.fl = c.take(m);
-    t.gh = c.take(m);
-    t.tmp_bytes = std::max(hint_tmp_bytes(sm), hint_tmp_bytes(n_files));
-    t.tmp = c.take(t.tmp_bytes);
+    t.carve(c, m, t.a, std::max(hint_tmp_bytes(sm), hint_tmp_bytes(n_files)));
     if (w) *w = t;
     return c.bytes();
 }
@@ -435,39 +407,24 @@ inline int launch_hm_plan(const HmIn &in, int64_t index_interval, uint64_t *item
     hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(HintCounters), s);
     if (e != hipSuccess) return (int)e;
     if ((e = hipMemsetAsync(w.hm, 0, sizeof(HmCounters), s)) != hipSuccess) return (int)e;
-    size_t tb;
-    auto scan32 = [&](size_t n) {
-        tb = w.tmp_bytes;
-        return rocprim::exclusive_scan(w.tmp, tb, (const uint32_t *)w.fa, w.fb, 0u, n, rocprim::plus<uint32_t>(), s);
-    };
-    auto scan_acc = [&](const HintAcc *from, HintAcc *to, size_t n) {
-        tb = w.tmp_bytes;
-        return rocprim::exclusive_scan(w.tmp, tb, from, to, HintAcc{0, 0}, n, HintAccPlus(), s);
-    };
     // the sources' items: heads, stretches, counts, positions
     hipLaunchKernelGGL(k_hm_head, GF, B, 0, s, in, w.src, w.unproven, w.sv, w.cnt, w.hm);
-    if ((e = scan_acc(w.sv, w.sb, in.n_files)) != hipSuccess) return (int)e;
+    if ((e = w.scan(w.sv, w.sb, in.n_files, HintAccPlus(), s)) != hipSuccess) return (int)e;
     const HmStr st{w.src, w.sv, w.sb, w.unproven, in.n_files, in.cap};
     hipLaunchKernelGGL(k_hm_count, GS, B, 0, s, in, st, w.unproven, w.a, w.hm);
     hipLaunchKernelGGL(k_hm_settle, GS, B, 0, s, in, st, w.a, w.hm);
     // the scan covers the most stretches there can be; the kernels read the first S sums only
-    if ((e = scan_acc(w.a, w.b, (size_t)in.cap + in.n_files)) != hipSuccess) return (int)e;
+    if ((e = w.scan(w.a, w.b, (size_t)in.cap + in.n_files, HintAccPlus(), s)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_hm_fill, GS, B, 0, s, in, st, (const HintAcc *)w.a, (const HintAcc *)w.b, w.pos, w.sid, w.hm);
     const HmKey K{in.hints, w.pos, in.cap};
     hipLaunchKernelGGL(k_hm_sorted, G, B, 0, s, K, (const uint32_t *)w.sid, w.hm);
     // by CmpKey, then stably by keyhash: a run of equal hash is in position order
     hipLaunchKernelGGL(k_hm_cmpkey, G, B, 0, s, in, (const uint64_t *)w.pos, (const uint32_t *)w.sid, w.key_in, w.val_in,
                        w.cnt, w.hm);
-    tb = w.tmp_bytes;
-    e = rocprim::radix_sort_pairs(w.tmp, tb, (const uint64_t *)w.key_in, w.key_s, (const uint32_t *)w.val_in, w.val_s,
-                                  (size_t)M, 0, 64, s);
-    if (e != hipSuccess) return (int)e;
+    if ((e = w.sort(w.val_in, w.val_s, M, s)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_hm_hashkey, G, B, 0, s, in, (const uint64_t *)w.pos, (const uint32_t *)w.val_s, w.key_in,
                        (const HintCounters *)w.cnt);
-    tb = w.tmp_bytes;
-    e = rocprim::radix_sort_pairs(w.tmp, tb, (const uint64_t *)w.key_in, w.key_s, (const uint32_t *)w.val_s, w.val_in,
-                                  (size_t)M, 0, 64, s);
-    if (e != hipSuccess) return (int)e;
+    if ((e = w.sort(w.val_s, w.val_in, M, s)) != hipSuccess) return (int)e;
     // (keyhash, key, position) order and the groups
     hipLaunchKernelGGL(k_hint_runs<HmKey>, G, B, 0, s, K, (const uint64_t *)w.key_s, (const uint32_t *)w.val_in, w.fl,
                        w.gh, w.val_r, w.list, w.cnt);
@@ -476,27 +433,18 @@ inline int launch_hm_plan(const HmIn &in, int64_t index_interval, uint64_t *item
     // the merged items, the collision items among them, the file offsets
     hipLaunchKernelGGL(k_hm_cflag, G, B, 0, s, (const uint64_t *)w.key_s, (const uint8_t *)w.gh, M, w.fa,
                        (const HintCounters *)w.cnt);
-    if ((e = scan32((size_t)M + 1)) != hipSuccess) return (int)e;
+    if ((e = w.scan(w.fa, w.fb, (size_t)M + 1, rocprim::plus<uint32_t>(), s)) != hipSuccess) return (int)e;
     HintAcc *itemv = w.a, *items = w.b;
     hipLaunchKernelGGL(k_hm_winners, G, B, 0, s, K, (const uint64_t *)w.key_s, (const uint8_t *)w.gh,
                        (const uint32_t *)w.val_r, (const uint32_t *)w.fb, w.fa, itemv, (const HintCounters *)w.cnt);
-    if ((e = scan32(M)) != hipSuccess) return (int)e;
-    if ((e = scan_acc(itemv, items, M)) != hipSuccess) return (int)e;
+    if ((e = w.scan(w.fa, w.fb, M, rocprim::plus<uint32_t>(), s)) != hipSuccess) return (int)e;
+    if ((e = w.scan(itemv, items, M, HintAccPlus(), s)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_hm_emit, G, B, 0, s, in, (const uint64_t *)w.pos, (const uint32_t *)w.sid,
                        (const HintAcc *)itemv, (const HintAcc *)items, (const uint32_t *)w.val_r,
                        (const uint32_t *)w.fa, (const uint32_t *)w.fb, item_src, item_chunk, item_off, coll_item, w.cnt,
                        w.hm);
-    // the index entries, as launch_hint_plan
-    const int64_t thr = (int64_t)((uint64_t)index_interval - kHintItem - 256);
-    uint32_t *J = w.val_in, *J2 = w.val_s;
-    hipLaunchKernelGGL(k_hint_next, G, B, 0, s, (const uint64_t *)item_off, thr, M, J, w.fa, w.cnt);
-    hipLaunchKernelGGL(k_hint_seed, dim3(1), dim3(1), 0, s, (const HintCounters *)w.cnt, w.fa);
-    for (uint64_t reach = 1; reach < (uint64_t)M + 1; reach <<= 1) {
-        hipLaunchKernelGGL(k_hint_double, G, B, 0, s, (const HintCounters *)w.cnt, (const uint32_t *)J, J2, w.fa);
-        std::swap(J, J2);
-    }
-    if ((e = scan32((size_t)M + 1)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_hint_index, G, B, 0, s, (const uint32_t *)w.fa, (const uint32_t *)w.fb, index_item, w.cnt);
+    // the index entries
+    if ((e = launch_hint_index(item_off, index_interval, M, w, w.cnt, index_item, s)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_hm_totals, dim3(1), dim3(1), 0, s, totals, (const HintCounters *)w.cnt,
                        (const HmCounters *)w.hm);
     return (int)hipGetLastError();

@@ -1,5 +1,5 @@
 // qlzx_recfile.h -- what the record-file kernels share (qlzx_replay.hip, qlzx_read.hip,
-// qlzx_write.hip, qlzx_gc.hip, qlzx_hint.hip): the format's constants, readRecordAt's checks
+// qlzx_write.hip, qlzx_gc.hip, and through qlzx_hint_fmt.h the hint sources): the format's constants, readRecordAt's checks
 // (store/datafile.go:114-170), the workspace carver, the wave sum, the stream compaction (three
 // scan kernels behind launch_compact), the u64 offset scan k_rp_dstoff, and the long-record
 // machinery: the list of records whose CRC span exceeds kRpLong, the segment accumulator, and

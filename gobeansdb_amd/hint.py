@@ -50,6 +50,30 @@ class HintSplit:
     skipped: int         # consumed records that failed the key guards (never a replay's own records)
 
 
+def _u64(v, dev) -> torch.Tensor:
+    """v as a device tensor of u64 bits (int64)."""
+    return torch.from_numpy(np.asarray(v, dtype=np.uint64).view(np.int64)).to(dev)
+
+
+def _u32(v, dev) -> torch.Tensor:
+    """v as a device tensor of u32 bits (int32)."""
+    return torch.from_numpy(np.asarray(v, dtype=np.uint32).view(np.int32)).to(dev)
+
+
+def _wide(t, lo: int, hi: int) -> int:
+    """The 64-bit total whose halves are t[lo] and t[hi]."""
+    return int(t[lo]) | (int(t[hi]) << 32)
+
+
+def _pack(files, stream):
+    """The files as one device buffer: (buffer, offsets, lengths).  On the device: the files never leave it."""
+    lens = [int(f.numel()) for f in files]
+    offs = [sum(lens[:i]) for i in range(len(files))]
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        hints = torch.cat([f.reshape(-1) for f in files]) if files else torch.empty(0, dtype=torch.uint8)
+    return hints, offs, lens
+
+
 def keyhash(keys: batch.BlockBatch, stream=None) -> torch.Tensor:
     """getKeyHashDefalut of every block: int64 [n] (the u64's bits)."""
     L = _lib.lib()
@@ -109,9 +133,9 @@ def build_split(res: replay.ReplayResult, first: int = 0, split_cap: int = SPLIT
         t[_lib.HINT_DATASIZE], t[_lib.HINT_INDEX_OFF_LO] = max_offset, 16
     if t[_lib.HINT_STATUS] != 0:
         raise _lib.QlzxError("qlzx_hint_write: the file does not fit its buffer")
-    nbytes = int(t[_lib.HINT_BYTES_LO]) | (int(t[_lib.HINT_BYTES_HI]) << 32)
+    nbytes = _wide(t, _lib.HINT_BYTES_LO, _lib.HINT_BYTES_HI)
     return HintSplit(out[:nbytes], int(t[_lib.HINT_NUM_KEY]), int(t[_lib.HINT_DATASIZE]),
-                     int(t[_lib.HINT_INDEX_OFF_LO]) | (int(t[_lib.HINT_INDEX_OFF_HI]) << 32),
+                     _wide(t, _lib.HINT_INDEX_OFF_LO, _lib.HINT_INDEX_OFF_HI),
                      int(t[_lib.HINT_N_INDEX]), int(t[_lib.HINT_CONSUMED]), int(t[_lib.HINT_SKIPPED]))
 
 
@@ -169,10 +193,8 @@ def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_inter
     cap = max(cap, 1)                               # a source without room for an item is the device's verdict
     out_cap = 16 + room + 16 * cap if write else 0  # always enough: no read-back before the write
     st_ = batch._stream()
-    u64 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.uint64).view(np.int64)).to(dev)
-    off_d, len_d = u64([int(x) for x in file_off]), u64(lens)
-    chunk_d = torch.from_numpy(np.asarray([int(c) & 0xFFFFFFFF for c in chunk_ids],
-                                          dtype=np.uint32).view(np.int32)).to(dev)
+    off_d, len_d = _u64([int(x) for x in file_off], dev), _u64(lens, dev)
+    chunk_d = _u32([int(c) & 0xFFFFFFFF for c in chunk_ids], dev)
     item_src, item_off = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(2))
     item_chunk, index_item, coll_item = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
     totals = torch.zeros(12, dtype=torch.int32, device=dev)
@@ -208,9 +230,9 @@ def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_inter
             collisions.append((int.from_bytes(b[0:8], "little"), b[23:23 + ksz], int(c),
                                int.from_bytes(b[12:16], "little"), int.from_bytes(b[16:20], "little", signed=True),
                                int.from_bytes(b[20:22], "little")))
-    nb = int(t[_lib.HM_BYTES_LO]) | (int(t[_lib.HM_BYTES_HI]) << 32)
+    nb = _wide(t, _lib.HM_BYTES_LO, _lib.HM_BYTES_HI)
     return HintMerged(out[:nb] if write else empty, int(t[_lib.HM_NUM_KEY]), int(t[_lib.HM_DATASIZE]),
-                      int(t[_lib.HM_INDEX_OFF_LO]) | (int(t[_lib.HM_INDEX_OFF_HI]) << 32), int(t[_lib.HM_N_INDEX]),
+                      _wide(t, _lib.HM_INDEX_OFF_LO, _lib.HM_INDEX_OFF_HI), int(t[_lib.HM_N_INDEX]),
                       int(t[_lib.HM_ITEMS_READ]), collisions)
 
 
@@ -223,12 +245,7 @@ def merge(files, chunk_ids, index_interval: int = INDEX_INTERVAL, write: bool = 
     files = list(files)
     if not files:
         return merge_packed(torch.empty(0, dtype=torch.uint8), [], [], [], index_interval, write)
-    lens = [int(f.numel()) for f in files]
-    offs = [0] * len(files)
-    for i in range(1, len(files)):
-        offs[i] = offs[i - 1] + lens[i - 1]
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        hints = torch.cat([f.reshape(-1) for f in files])      # on the device: the files never leave it
+    hints, offs, lens = _pack(files, stream)
     return merge_packed(hints, offs, lens, chunk_ids, index_interval, write, None, workspace, stream)
 
 
@@ -269,11 +286,9 @@ def lookup_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, keys: batc
     item_src = torch.zeros(n, dtype=torch.int64, device=dev)
     if n == 0 or n_files == 0:                      # no file: every key is a miss
         return HintLookup(status, hit_file, chunk, offset, ver, vhash, item_src, (0, n, 0, 0))
-    u64 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.uint64).view(np.int64)).to(dev)
-    u32 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.uint32).view(np.int32)).to(dev)
-    off_d, len_d = u64([int(x) for x in file_off]), u64(lens)
-    chunk_d = u32([int(c) & 0xFFFFFFFF for c in chunk_ids])
-    flag_d = u32([_lib.HL_FILE_MERGED if i == merged else 0 for i in range(n_files)])
+    off_d, len_d = _u64([int(x) for x in file_off], dev), _u64(lens, dev)
+    chunk_d = _u32([int(c) & 0xFFFFFFFF for c in chunk_ids], dev)
+    flag_d = _u32([_lib.HL_FILE_MERGED if i == merged else 0 for i in range(n_files)], dev)
     totals = torch.zeros(4, dtype=torch.int32, device=dev)
     ws_bytes = L.qlzx_hint_lookup_workspace_size(n, n_files)
     ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
@@ -299,11 +314,5 @@ def lookup(files, chunk_ids, keys: batch.BlockBatch, merged: int | None = None, 
     key above a file's last item usually ends in HL_ERR, which ends the search; bounded=True ends
     the scan at the index and goes on to the next file (what a multi-GET or a GC liveness pass
     wants).  keyhash (int64 [n]) replaces the default key hash.  The results stay on the device; totals is read back once."""
-    files = list(files)
-    lens = [int(f.numel()) for f in files]
-    offs = [0] * len(files)
-    for i in range(1, len(files)):
-        offs[i] = offs[i - 1] + lens[i - 1]
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        hints = torch.cat([f.reshape(-1) for f in files]) if files else torch.empty(0, dtype=torch.uint8)
+    hints, offs, lens = _pack(list(files), stream)
     return lookup_packed(hints, offs, lens, chunk_ids, keys, merged, bounded, keyhash, workspace, stream)
