@@ -27,9 +27,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, batch
-from .record import _copy, _dev_u32, _dev_u64
-from .replay import BODY_MAX, HDR, MAX_KEY_LEN
+from . import _dev, _lib, batch
+from ._dev import on_stream, ptr
+from .record import BODY_MAX, HDR, MAX_KEY_LEN
 
 DATA_FILE_MAX = 4000 << 20   # store/config_default.go:39
 
@@ -95,10 +95,11 @@ class GCBatch:
         w = (self.status == _lib.GC_WRITTEN).cpu().numpy()
         chunks = self.chunks or [self.out[:0]]
         return GCResult(chunks, self.new_chunk.cpu().numpy()[w].astype(np.int32),
-                        self.new_off.cpu().numpy().view(np.uint64)[w],
-                        self.crc.cpu().numpy().view(np.uint32)[w], int(self.totals[6]))
+                        self.new_off.cpu().numpy().view(np.uint64)[w], _dev.readback(self.crc)[w],
+                        int(self.totals[6]))
 
 
+@on_stream
 def rewrite_batch(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_head: int = 0,
                   data_file_max: int = DATA_FILE_MAX, next_heads=(), max_chunks: int | None = None,
                   out: torch.Tensor | None = None, stream=None) -> GCBatch:
@@ -109,9 +110,6 @@ def rewrite_batch(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor,
     (default: as many as the library takes) are used, later survivors get GC_NO_CHUNK.  `out`
     (optional, 16-B aligned, not overlapping data) receives the chunks packed back to back;
     pad256(len(data)) bytes always suffice for record offsets that came from replay.index."""
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return rewrite_batch(data, rec_off, keep, dst_head, data_file_max, next_heads, max_chunks, out, None)
     L = _lib.lib()
     dev = data.device
     size, n = int(data.numel()), int(rec_off.numel())
@@ -124,10 +122,10 @@ def rewrite_batch(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor,
     heads = np.zeros(max_chunks, np.uint64)                # chunk_head(c) for every c: 0 past next_heads
     known = [int(dst_head), *map(int, next_heads)][:max_chunks]
     heads[:len(known)] = known
-    heads = _dev_u64(heads, dev)
+    heads = _dev.u64(heads, dev)
     result = torch.tensor([n, 0, 0, 0], dtype=torch.int32, device=dev)
     keep8 = keep.to(device=dev, dtype=torch.uint8).contiguous()
-    rec_off = rec_off.to(device=dev, dtype=torch.int64).contiguous()
+    rec_off = _dev.u64(rec_off, dev)
     status = torch.empty(cap, dtype=torch.int32, device=dev)
     new_chunk, crc = torch.empty_like(status), torch.empty_like(status)
     new_off = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -139,23 +137,24 @@ def rewrite_batch(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor,
     ws_bytes = L.qlzx_gc_workspace_size(cap, max_chunks)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     if n:
-        _lib.check(L.qlzx_gc_plan(batch._ptr(data) if size else None, size, rec_off.data_ptr(), result.data_ptr(),
+        _lib.check(L.qlzx_gc_plan(ptr(data), size, rec_off.data_ptr(), result.data_ptr(),
                                   cap, keep8.data_ptr(), MAX_KEY_LEN, BODY_MAX, data_file_max, heads.data_ptr(),
                                   max_chunks, status.data_ptr(), new_chunk.data_ptr(), new_off.data_ptr(),
                                   chunk_base.data_ptr(), chunk_bytes.data_ptr(), totals.data_ptr(), ws.data_ptr(),
                                   ws_bytes, st_), "qlzx_gc_plan")
-        _lib.check(L.qlzx_gc_rewrite(batch._ptr(data) if size else None, size, rec_off.data_ptr(),
+        _lib.check(L.qlzx_gc_rewrite(ptr(data), size, rec_off.data_ptr(),
                                      result.data_ptr(), cap, heads.data_ptr(), max_chunks, new_chunk.data_ptr(),
                                      new_off.data_ptr(), chunk_base.data_ptr(), out.data_ptr(), int(out.numel()),
                                      status.data_ptr(), crc.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes,
                                      st_), "qlzx_gc_rewrite")
-    t = totals.cpu().numpy().view(np.uint32)               # the read-backs: totals and the chunk sizes
+    t = _dev.readback(totals)                              # the read-backs: totals and the chunk sizes
     cb = chunk_bytes[:max(int(t[3]), 1)].cpu().numpy().view(np.uint64)[:int(t[3])]
     base = np.concatenate([[0], np.cumsum(cb.astype(np.int64))])
     chunks = [out[int(base[c]):int(base[c + 1])] for c in range(len(cb))]
     return GCBatch(status[:n], new_chunk[:n], new_off[:n], crc[:n], chunks, out, t, cb)
 
 
+@on_stream
 def rewrite(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_head: int = 0,
             data_file_max: int = DATA_FILE_MAX, stream=None, next_heads=()) -> GCResult:
     """Rewrite the kept records of the chunk `data` (record offsets `rec_off` in reader order,
@@ -181,7 +180,7 @@ def rewrite(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_h
         end = int(off[sel[-1]] + recsize[sel[-1]]) if len(sel) else base
         buf = torch.zeros(max(end - base, 1), dtype=torch.uint8, device=dev)[: end - base]
         if len(sel):   # record bytes; the zero padding is the fresh buffer's (datafile.go:322-327)
-            _copy(data, src_off[sel], size[sel].astype(np.uint32), buf, off[sel] - np.uint64(base), stream)
+            batch.copy_blocks(data, src_off[sel], size[sel], buf, off[sel] - np.uint64(base))
         chunks.append(buf)
     # encodeHeader/getCRC over each rewritten record, written into its header
     crc = np.zeros(n, np.uint32)
@@ -190,8 +189,7 @@ def rewrite(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_h
         if not len(sel):
             continue
         local = off[sel] - np.uint64(chunk_head(c, dst_head, next_heads))
-        got = batch.crc32(batch.BlockBatch(buf, _dev_u64(local + np.uint64(4), dev),
-                                           _dev_u32((size[sel] - 4).astype(np.uint32), dev)), stream=stream)
-        buf.view(torch.int32)[torch.from_numpy((local // 4).astype(np.int64)).to(dev)] = got
-        crc[sel] = got.cpu().numpy().view(np.uint32)
+        got = batch.crc32(batch.BlockBatch(buf, _dev.u64(local + np.uint64(4), dev), _dev.u32(size[sel] - 4, dev)))
+        buf.view(torch.int32)[_dev.u64(local // 4, dev)] = got
+        crc[sel] = _dev.readback(got)
     return GCResult(chunks, chunk, off, crc, int((crc != stored_crc).sum()))

@@ -27,13 +27,13 @@ HintBuffer.Get stay out of scope; the caller owns the files' bytes.
 """
 from __future__ import annotations
 
-import contextlib
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from . import _lib, batch, replay
+from . import _dev, _lib, batch, replay
+from ._dev import on_stream, ptr, wide
 
 SPLIT_CAP = _lib.HINT_SPLIT_CAP
 INDEX_INTERVAL = _lib.HINT_INDEX_INTERVAL
@@ -50,39 +50,37 @@ class HintSplit:
     skipped: int         # consumed records that failed the key guards (never a replay's own records)
 
 
-def _u64(v, dev) -> torch.Tensor:
-    """v as a device tensor of u64 bits (int64)."""
-    return torch.from_numpy(np.asarray(v, dtype=np.uint64).view(np.int64)).to(dev)
-
-
-def _u32(v, dev) -> torch.Tensor:
-    """v as a device tensor of u32 bits (int32)."""
-    return torch.from_numpy(np.asarray(v, dtype=np.uint32).view(np.int32)).to(dev)
-
-
-def _wide(t, lo: int, hi: int) -> int:
-    """The 64-bit total whose halves are t[lo] and t[hi]."""
-    return int(t[lo]) | (int(t[hi]) << 32)
-
-
-def _pack(files, stream):
+def _pack(files):
     """The files as one device buffer: (buffer, offsets, lengths).  On the device: the files never leave it."""
     lens = [int(f.numel()) for f in files]
     offs = [sum(lens[:i]) for i in range(len(files))]
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        hints = torch.cat([f.reshape(-1) for f in files]) if files else torch.empty(0, dtype=torch.uint8)
+    hints = torch.cat([f.reshape(-1) for f in files]) if files else torch.empty(0, dtype=torch.uint8)
     return hints, offs, lens
 
 
+def _files(what: str, file_off, file_len, chunk_ids, dev):
+    """The per-file arguments of merge and lookup, checked and uploaded: (lengths on the host,
+    offsets, lengths and chunk ids on the device)."""
+    lens = [int(x) for x in file_len]
+    if not (len(file_off) == len(chunk_ids) == len(lens)):
+        raise ValueError(f"{what}: one offset, length and chunk id per file")
+    if not lens:
+        return lens, None, None, None
+    return (lens, _dev.u64([int(x) for x in file_off], dev), _dev.u64(lens, dev),
+            _dev.u32([int(c) & 0xFFFFFFFF for c in chunk_ids], dev))
+
+
+@on_stream
 def keyhash(keys: batch.BlockBatch, stream=None) -> torch.Tensor:
     """getKeyHashDefalut of every block: int64 [n] (the u64's bits)."""
     L = _lib.lib()
     out = torch.empty(keys.n, dtype=torch.int64, device=keys.data.device)
     _lib.check(L.qlzx_keyhash_batch(keys.data.data_ptr(), keys.off.data_ptr(), keys.length.data_ptr(), keys.n,
-                                    out.data_ptr(), batch._stream(stream)), "qlzx_keyhash_batch")
+                                    out.data_ptr(), batch._stream()), "qlzx_keyhash_batch")
     return out
 
 
+@on_stream
 def build_split(res: replay.ReplayResult, first: int = 0, split_cap: int = SPLIT_CAP,
                 index_interval: int = INDEX_INTERVAL, chunk_id: int = 0, max_offset: int = 0,
                 keyhash: torch.Tensor | None = None, workspace: batch.Workspace | None = None,
@@ -90,9 +88,6 @@ def build_split(res: replay.ReplayResult, first: int = 0, split_cap: int = SPLIT
     """One split file from the records res[first:]: as many as HintBuffer.Set takes with SplitCap =
     split_cap.  keyhash (int64 [n], optional) replaces the default key hash, as the reference's
     getKeyHash variable can.  One read-back: totals."""
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return build_split(res, first, split_cap, index_interval, chunk_id, max_offset, keyhash, workspace, None)
     L = _lib.lib()
     data = res.data
     dev = data.device
@@ -100,13 +95,12 @@ def build_split(res: replay.ReplayResult, first: int = 0, split_cap: int = SPLIT
     st_ = batch._stream()
     cap = max(n, 1)
     result = torch.tensor([n, 0, 0, 0], dtype=torch.int32, device=dev)
-    rec_off = res.offset.to(device=dev, dtype=torch.int64).contiguous()
-    hdr = res.header.to(device=dev, dtype=torch.int32).contiguous()
+    rec_off, hdr = _dev.u64(res.offset, dev), _dev.i32(res.header, dev)
     vh16 = res.vhash.to(device=dev, dtype=torch.int16).contiguous()
     if keyhash is not None:
         if keyhash.numel() != n:
             raise ValueError("keyhash: one per record")
-        keyhash = keyhash.to(device=dev, dtype=torch.int64).contiguous()
+        keyhash = _dev.u64(keyhash, dev)
     item_rec = torch.empty(cap, dtype=torch.int32, device=dev)
     index_item = torch.empty(cap, dtype=torch.int32, device=dev)
     item_hash = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -117,28 +111,29 @@ def build_split(res: replay.ReplayResult, first: int = 0, split_cap: int = SPLIT
     ws_bytes = L.qlzx_hint_workspace_size(cap)
     ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
     if n:
-        _lib.check(L.qlzx_hint_plan(batch._ptr(data) if size else None, size, rec_off.data_ptr(), result.data_ptr(),
-                                    cap, hdr.data_ptr(), batch._ptr(keyhash), first, split_cap, index_interval,
+        _lib.check(L.qlzx_hint_plan(ptr(data), size, rec_off.data_ptr(), result.data_ptr(),
+                                    cap, hdr.data_ptr(), ptr(keyhash), first, split_cap, index_interval,
                                     max_offset, item_rec.data_ptr(), item_hash.data_ptr(), item_off.data_ptr(),
                                     index_item.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes, st_),
                    "qlzx_hint_plan")
-        _lib.check(L.qlzx_hint_write(batch._ptr(data) if size else None, size, rec_off.data_ptr(), cap,
+        _lib.check(L.qlzx_hint_write(ptr(data), size, rec_off.data_ptr(), cap,
                                      hdr.data_ptr(), vh16.data_ptr(), chunk_id, item_rec.data_ptr(),
                                      item_hash.data_ptr(), item_off.data_ptr(), index_item.data_ptr(),
                                      out.data_ptr(), out_cap, totals.data_ptr(), ws.data_ptr(), ws_bytes, st_),
                    "qlzx_hint_write")
-        t = totals.cpu().numpy().view(np.uint32)   # the read-back
+        t = _dev.readback(totals)                  # the read-back
     else:
         t = np.zeros(10, np.uint32)
         t[_lib.HINT_DATASIZE], t[_lib.HINT_INDEX_OFF_LO] = max_offset, 16
     if t[_lib.HINT_STATUS] != 0:
         raise _lib.QlzxError("qlzx_hint_write: the file does not fit its buffer")
-    nbytes = _wide(t, _lib.HINT_BYTES_LO, _lib.HINT_BYTES_HI)
+    nbytes = wide(t, _lib.HINT_BYTES_LO)
     return HintSplit(out[:nbytes], int(t[_lib.HINT_NUM_KEY]), int(t[_lib.HINT_DATASIZE]),
-                     _wide(t, _lib.HINT_INDEX_OFF_LO, _lib.HINT_INDEX_OFF_HI),
+                     wide(t, _lib.HINT_INDEX_OFF_LO),
                      int(t[_lib.HINT_N_INDEX]), int(t[_lib.HINT_CONSUMED]), int(t[_lib.HINT_SKIPPED]))
 
 
+@on_stream
 def build(res: replay.ReplayResult, split_cap: int = SPLIT_CAP, index_interval: int = INDEX_INTERVAL,
           chunk_id: int = 0, max_offset: int = 0, keyhash: torch.Tensor | None = None,
           workspace: batch.Workspace | None = None, stream=None) -> list[HintSplit]:
@@ -148,7 +143,7 @@ def build(res: replay.ReplayResult, split_cap: int = SPLIT_CAP, index_interval: 
     ws = workspace or batch.Workspace(res.data.device)
     out, first = [], 0
     while first < res.n:
-        sp = build_split(res, first, split_cap, index_interval, chunk_id, max_offset, keyhash, ws, stream)
+        sp = build_split(res, first, split_cap, index_interval, chunk_id, max_offset, keyhash, ws)
         if sp.consumed == 0:
             raise _lib.QlzxError("qlzx_hint_plan consumed no record")
         out.append(sp)
@@ -169,21 +164,17 @@ class HintMerged:
     #                      is shared by two or more keys, in merged order
 
 
+@on_stream
 def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_interval: int = INDEX_INTERVAL,
                  write: bool = True, cap: int | None = None, workspace: batch.Workspace | None = None,
                  stream=None) -> HintMerged:
     """merge() for a caller that holds every source in one device buffer: source i is
     hints[file_off[i] : file_off[i] + file_len[i]] with the reader's chunk id chunk_ids[i].
     cap (the most items the sources may hold) defaults to what their lengths allow."""
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return merge_packed(hints, file_off, file_len, chunk_ids, index_interval, write, cap, workspace, None)
     L = _lib.lib()
     dev = hints.device
-    lens = [int(x) for x in file_len]
+    lens, off_d, len_d, chunk_d = _files("merge", file_off, file_len, chunk_ids, dev)
     n_files, nbytes = len(lens), int(hints.numel())
-    if not (len(file_off) == len(chunk_ids) == n_files):
-        raise ValueError("merge: one offset, length and chunk id per source")
     room = sum(max(x - 16, 0) for x in lens)
     if cap is None:
         cap = room // 23
@@ -193,15 +184,13 @@ def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_inter
     cap = max(cap, 1)                               # a source without room for an item is the device's verdict
     out_cap = 16 + room + 16 * cap if write else 0  # always enough: no read-back before the write
     st_ = batch._stream()
-    off_d, len_d = _u64([int(x) for x in file_off], dev), _u64(lens, dev)
-    chunk_d = _u32([int(c) & 0xFFFFFFFF for c in chunk_ids], dev)
     item_src, item_off = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(2))
     item_chunk, index_item, coll_item = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
     totals = torch.zeros(12, dtype=torch.int32, device=dev)
     out = torch.empty(out_cap, dtype=torch.uint8, device=dev)
     ws_bytes = L.qlzx_hint_merge_workspace_size(nbytes, n_files, cap)
     ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
-    hp = batch._ptr(hints) if nbytes else None
+    hp = ptr(hints)
     _lib.check(L.qlzx_hint_merge_plan(hp, nbytes, off_d.data_ptr(), len_d.data_ptr(), chunk_d.data_ptr(), n_files, cap,
                                       index_interval, item_src.data_ptr(), item_chunk.data_ptr(), item_off.data_ptr(),
                                       index_item.data_ptr(), coll_item.data_ptr(), totals.data_ptr(), ws.data_ptr(),
@@ -210,7 +199,7 @@ def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_inter
         _lib.check(L.qlzx_hint_merge_write(hp, nbytes, cap, item_src.data_ptr(), item_chunk.data_ptr(),
                                            item_off.data_ptr(), index_item.data_ptr(), out.data_ptr(), out_cap,
                                            totals.data_ptr(), ws.data_ptr(), ws_bytes, st_), "qlzx_hint_merge_write")
-    t = totals.cpu().numpy().view(np.uint32)        # the read-back
+    t = _dev.readback(totals)                       # the read-back
     status = int(t[_lib.HM_STATUS])
     if status != _lib.HM_OK:
         name = _lib.HM_NAMES[status] if status < len(_lib.HM_NAMES) else str(status)
@@ -223,19 +212,20 @@ def merge_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, index_inter
         src = item_src[ci]
         span = (src[:, None] + torch.arange(23 + 255, device=dev)[None, :]).clamp_(max=nbytes - 1)
         raw = hints[span].cpu().numpy()
-        chunks = item_chunk[ci].cpu().numpy().view(np.uint32)
+        chunks = _dev.readback(item_chunk[ci])
         for row, c in zip(raw, chunks):
             b = row.tobytes()
             ksz = b[22]
             collisions.append((int.from_bytes(b[0:8], "little"), b[23:23 + ksz], int(c),
                                int.from_bytes(b[12:16], "little"), int.from_bytes(b[16:20], "little", signed=True),
                                int.from_bytes(b[20:22], "little")))
-    nb = _wide(t, _lib.HM_BYTES_LO, _lib.HM_BYTES_HI)
+    nb = wide(t, _lib.HM_BYTES_LO)
     return HintMerged(out[:nb] if write else empty, int(t[_lib.HM_NUM_KEY]), int(t[_lib.HM_DATASIZE]),
-                      _wide(t, _lib.HM_INDEX_OFF_LO, _lib.HM_INDEX_OFF_HI), int(t[_lib.HM_N_INDEX]),
+                      wide(t, _lib.HM_INDEX_OFF_LO), int(t[_lib.HM_N_INDEX]),
                       int(t[_lib.HM_ITEMS_READ]), collisions)
 
 
+@on_stream
 def merge(files, chunk_ids, index_interval: int = INDEX_INTERVAL, write: bool = True,
           workspace: batch.Workspace | None = None, stream=None) -> HintMerged:
     """hintMgr.Merge over split files in device memory (HintSplit.file straight from build());
@@ -245,8 +235,8 @@ def merge(files, chunk_ids, index_interval: int = INDEX_INTERVAL, write: bool = 
     files = list(files)
     if not files:
         return merge_packed(torch.empty(0, dtype=torch.uint8), [], [], [], index_interval, write)
-    hints, offs, lens = _pack(files, stream)
-    return merge_packed(hints, offs, lens, chunk_ids, index_interval, write, None, workspace, stream)
+    hints, offs, lens = _pack(files)
+    return merge_packed(hints, offs, lens, chunk_ids, index_interval, write, None, workspace)
 
 
 @dataclass
@@ -261,48 +251,43 @@ class HintLookup:
     totals: tuple            # (found, miss, err, bad_file), read back once
 
 
+@on_stream
 def lookup_packed(hints: torch.Tensor, file_off, file_len, chunk_ids, keys: batch.BlockBatch,
                   merged: int | None = None, bounded: bool = False, keyhash: torch.Tensor | None = None,
                   workspace: batch.Workspace | None = None, stream=None) -> HintLookup:
     """lookup() for a caller that holds every file in one device buffer: file i is
     hints[file_off[i] : file_off[i] + file_len[i]] with the chunk id chunk_ids[i], in search order."""
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return lookup_packed(hints, file_off, file_len, chunk_ids, keys, merged, bounded, keyhash, workspace, None)
     L = _lib.lib()
     dev = keys.data.device
-    lens = [int(x) for x in file_len]
+    lens, off_d, len_d, chunk_d = _files("lookup", file_off, file_len, chunk_ids, dev)
     n_files, nbytes, n = len(lens), int(hints.numel()), keys.n
-    if not (len(file_off) == len(chunk_ids) == n_files):
-        raise ValueError("lookup: one offset, length and chunk id per file")
     if merged is not None and not 0 <= merged < n_files:
         raise ValueError("lookup: merged is the index of a file")
     if keyhash is not None:
         if keyhash.numel() != n:
             raise ValueError("keyhash: one per key")
-        keyhash = keyhash.to(device=dev, dtype=torch.int64).contiguous()
+        keyhash = _dev.u64(keyhash, dev)
     status, hit_file, chunk, offset, ver = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(5))
     vhash = torch.zeros(n, dtype=torch.int16, device=dev)
     item_src = torch.zeros(n, dtype=torch.int64, device=dev)
     if n == 0 or n_files == 0:                      # no file: every key is a miss
         return HintLookup(status, hit_file, chunk, offset, ver, vhash, item_src, (0, n, 0, 0))
-    off_d, len_d = _u64([int(x) for x in file_off], dev), _u64(lens, dev)
-    chunk_d = _u32([int(c) & 0xFFFFFFFF for c in chunk_ids], dev)
-    flag_d = _u32([_lib.HL_FILE_MERGED if i == merged else 0 for i in range(n_files)], dev)
+    flag_d = _dev.u32([_lib.HL_FILE_MERGED if i == merged else 0 for i in range(n_files)], dev)
     totals = torch.zeros(4, dtype=torch.int32, device=dev)
     ws_bytes = L.qlzx_hint_lookup_workspace_size(n, n_files)
     ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
     flags = _lib.HL_F_BOUNDED if bounded else 0     # the kernel (a wave or a lane per request) goes by n
-    _lib.check(L.qlzx_hint_lookup(batch._ptr(hints) if nbytes else None, nbytes, off_d.data_ptr(), len_d.data_ptr(),
+    _lib.check(L.qlzx_hint_lookup(ptr(hints), nbytes, off_d.data_ptr(), len_d.data_ptr(),
                                   chunk_d.data_ptr(), flag_d.data_ptr(), n_files, keys.data.data_ptr(),
-                                  keys.off.data_ptr(), keys.length.data_ptr(), batch._ptr(keyhash), n, flags,
+                                  keys.off.data_ptr(), keys.length.data_ptr(), ptr(keyhash), n, flags,
                                   status.data_ptr(), hit_file.data_ptr(), chunk.data_ptr(), offset.data_ptr(),
                                   ver.data_ptr(), vhash.data_ptr(), item_src.data_ptr(), totals.data_ptr(),
                                   ws.data_ptr(), ws_bytes, batch._stream()), "qlzx_hint_lookup")
-    t = totals.cpu().numpy().view(np.uint32)        # the read-back
+    t = _dev.readback(totals)                       # the read-back
     return HintLookup(status, hit_file, chunk, offset, ver, vhash, item_src, tuple(int(x) for x in t))
 
 
+@on_stream
 def lookup(files, chunk_ids, keys: batch.BlockBatch, merged: int | None = None, bounded: bool = False,
            keyhash: torch.Tensor | None = None, workspace: batch.Workspace | None = None,
            stream=None) -> HintLookup:
@@ -314,5 +299,5 @@ def lookup(files, chunk_ids, keys: batch.BlockBatch, merged: int | None = None, 
     key above a file's last item usually ends in HL_ERR, which ends the search; bounded=True ends
     the scan at the index and goes on to the next file (what a multi-GET or a GC liveness pass
     wants).  keyhash (int64 [n]) replaces the default key hash.  The results stay on the device; totals is read back once."""
-    hints, offs, lens = _pack(list(files), stream)
-    return lookup_packed(hints, offs, lens, chunk_ids, keys, merged, bounded, keyhash, workspace, stream)
+    hints, offs, lens = _pack(list(files))
+    return lookup_packed(hints, offs, lens, chunk_ids, keys, merged, bounded, keyhash, workspace)

@@ -22,20 +22,22 @@ offsets and the CRCs kept on the device.
 """
 from __future__ import annotations
 
-import struct
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from . import _lib, batch
+from . import _dev, _lib, batch
 
+# the record format, defined here for the whole package
+HDR = 24                   # store/datafile.go:66-88: crc, ts, flag, ver, ksz, vsz
+PADDING = 256              # store/item.go:20
 FLAG_COMPRESS = 0x00010000
 FLAG_CLIENT_COMPRESS = 0x00000010
+MAX_KEY_LEN = 250          # config/mc_config.go:6
+BODY_MAX = 50 << 20        # config/mc_config.go:7 ("50M")
 TRY_COMPRESS_SIZE = 10 * 1024
 COMPRESS_RATIO_LIMIT = np.float32(0.7)
-PADDING = 256
-HDR = 24
 NOT_COMPRESS = frozenset({"audio/wave", "audio/mpeg"})
 
 
@@ -86,14 +88,6 @@ class Encoded:
     crc: np.ndarray           # uint32 record CRCs
 
 
-def _dev_u64(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
-
-
-def _dev_u32(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).to(dev)
-
-
 def sniff_many(heads: np.ndarray, lens: np.ndarray, not_compress=NOT_COMPRESS) -> np.ndarray:
     """need_compress for many values at once: heads = the first bytes of each value (uint8
     [n, >= 12]), lens = the value lengths.  Same rows, order and masks as sniff()."""
@@ -112,6 +106,7 @@ def sniff_many(heads: np.ndarray, lens: np.ndarray, not_compress=NOT_COMPRESS) -
     return ~skip
 
 
+@_dev.on_stream
 def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, ts=None,
            not_compress=NOT_COMPRESS, workspace: batch.Workspace | None = None, stream=None) -> Encoded:
     """TryCompress + encodeHeader + padding for n records whose values live on the device.
@@ -123,7 +118,7 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
     flags = np.zeros(n, np.uint32) if flags is None else np.asarray(flags, np.uint32).copy()
     vers = np.zeros(n, np.int32) if vers is None else np.asarray(vers, np.int32)
     ts = np.zeros(n, np.uint32) if ts is None else np.asarray(ts, np.uint32)
-    vlen = values.length.cpu().numpy().view(np.uint32).astype(np.int64)
+    vlen = _dev.readback(values.length).astype(np.int64)
     voff = values.off.cpu().numpy().view(np.uint64)
     klen = np.fromiter(map(len, keys), np.int64, count=n)
 
@@ -143,11 +138,10 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
     bufs = [None, None]
     if len(ci):
         tlen = np.minimum(vlen[ci], TRY_COMPRESS_SIZE)
-        trial = batch.BlockBatch(values.data, _dev_u64(voff[ci], dev), _dev_u32(tlen, dev))
+        trial = batch.BlockBatch(values.data, _dev.u64(voff[ci], dev), _dev.u32(tlen, dev))
         crc0 = torch.zeros(len(ci), dtype=torch.int32, device=dev)
-        tdst, tcs, tst, tcrc = batch.compress(trial, crc_state=crc0, max_len=int(tlen.max()), workspace=ws,
-                                             stream=stream)
-        tcs_h = tcs.cpu().numpy().view(np.uint32).astype(np.int64)
+        tdst, tcs, tst, tcrc = batch.compress(trial, crc_state=crc0, max_len=int(tlen.max()), workspace=ws)
+        tcs_h = _dev.readback(tcs).astype(np.int64)
         if int((tst != 0).sum()):
             raise _lib.QlzxError("trial compress failed on the device")
         keep = (tcs_h.astype(np.float32) / tlen.astype(np.float32)) <= COMPRESS_RATIO_LIMIT   # :145
@@ -158,21 +152,21 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
         is_comp[r] = True
         c_off[r] = tdst.off.cpu().numpy().view(np.uint64)[kt]
         c_len[r] = tcs_h[kt]
-        c_crc[r] = tcrc.cpu().numpy().view(np.uint32)[kt] ^ np.uint32(0xFFFFFFFF)
+        c_crc[r] = _dev.readback(tcrc)[kt] ^ np.uint32(0xFFFFFFFF)
         fi = ci[full]
         if len(fi):
-            fsrc = batch.BlockBatch(values.data, _dev_u64(voff[fi], dev), _dev_u32(vlen[fi], dev))
+            fsrc = batch.BlockBatch(values.data, _dev.u64(voff[fi], dev), _dev.u32(vlen[fi], dev))
             fcrc0 = torch.zeros(len(fi), dtype=torch.int32, device=dev)
             fdst, fcs, fst, fcrc = batch.compress(fsrc, crc_state=fcrc0, max_len=int(vlen[fi].max()),
-                                                 workspace=ws, stream=stream)
+                                                 workspace=ws)
             if int((fst != 0).sum()):
                 raise _lib.QlzxError("compress failed on the device")
             bufs[1] = fdst.data
             is_comp[fi] = True
             c_src[fi] = 1
             c_off[fi] = fdst.off.cpu().numpy().view(np.uint64)
-            c_len[fi] = fcs.cpu().numpy().view(np.uint32).astype(np.int64)
-            c_crc[fi] = fcrc.cpu().numpy().view(np.uint32) ^ np.uint32(0xFFFFFFFF)
+            c_len[fi] = _dev.readback(fcs).astype(np.int64)
+            c_crc[fi] = _dev.readback(fcrc) ^ np.uint32(0xFFFFFFFF)
     # ---- stored value sizes / flags ----
     vsz = np.where(is_comp, c_len, vlen)
     flags = flags + np.where(is_comp, np.uint32(FLAG_COMPRESS), np.uint32(0)).astype(np.uint32)   # :159
@@ -180,9 +174,9 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
     raw_v = c_crc.copy()
     plain = np.nonzero(~is_comp)[0]
     if len(plain):
-        c = batch.crc32(batch.BlockBatch(values.data, _dev_u64(voff[plain], dev), _dev_u32(vlen[plain], dev)),
-                        init=torch.zeros(len(plain), dtype=torch.int32, device=dev), final_xor=0, stream=stream)
-        raw_v[plain] = c.cpu().numpy().view(np.uint32)
+        c = batch.crc32(batch.BlockBatch(values.data, _dev.u64(voff[plain], dev), _dev.u32(vlen[plain], dev)),
+                        init=torch.zeros(len(plain), dtype=torch.int32, device=dev), final_xor=0)
+        raw_v[plain] = _dev.readback(c)
     # ---- header[4:24] || key prefixes (16-B aligned staging), their raw CRC state from ~0, and
     # the combine with the value's raw CRC (datafile.go:66-76) ----
     pre_len = (20 + klen).astype(np.int64)
@@ -201,14 +195,13 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
             kstart[1:] = np.cumsum(klen)[:-1]
             pre[np.repeat(pre_off + 20 - kstart, klen) + np.arange(kall.size)] = kall
     pre_d = torch.from_numpy(pre).to(dev)
-    s_hk = batch.crc32(batch.BlockBatch(pre_d, _dev_u64(pre_off.astype(np.uint64), dev),
-                                        _dev_u32(pre_len.astype(np.uint32), dev)), final_xor=0, stream=stream)
+    s_hk = batch.crc32(batch.BlockBatch(pre_d, _dev.u64(pre_off, dev), _dev.u32(pre_len, dev)), final_xor=0)
     crc_d = torch.zeros(n, dtype=torch.int32, device=dev)
-    rv = _dev_u32(raw_v, dev)
-    lv = _dev_u32(vsz, dev)
+    rv = _dev.u32(raw_v, dev)
+    lv = _dev.u32(vsz, dev)
     _lib.check(L.qlzx_crc32_combine(s_hk.data_ptr(), rv.data_ptr(), lv.data_ptr(), n, 0xFFFFFFFF,
-                                    crc_d.data_ptr(), batch._stream(stream)), "qlzx_crc32_combine")
-    crc = crc_d.cpu().numpy().view(np.uint32).copy()
+                                    crc_d.data_ptr(), batch._stream()), "qlzx_crc32_combine")
+    crc = _dev.readback(crc_d).copy()
     # ---- assemble: crc || header tail || key || value, zero padding to 256 (datafile.go:307-330) ----
     rsize = (HDR + klen + vsz + 255) // 256 * 256
     roff = np.zeros(n, np.uint64)
@@ -217,18 +210,17 @@ def encode(keys: list[bytes], values: batch.BlockBatch, flags=None, vers=None, t
     total = int(rsize.sum())
     out = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
     # header tail + key (from the prefix staging) at off + 4
-    _copy(pre_d, pre_off.astype(np.uint64), pre_len.astype(np.uint32), out, roff + 4, stream)
+    batch.copy_blocks(pre_d, pre_off, pre_len, out, roff + 4)
     # values: raw ones from the value buffer, compressed ones from their compress buffers
+    voff_out = roff + HDR + klen.astype(np.uint64)
     if len(plain):
-        _copy(values.data, voff[plain], vlen[plain].astype(np.uint32), out,
-              roff[plain] + HDR + klen[plain].astype(np.uint64), stream)
+        batch.copy_blocks(values.data, voff[plain], vlen[plain], out, voff_out[plain])
     for b in (0, 1):
         rs = np.nonzero(is_comp & (c_src == b))[0]
         if len(rs):
-            _copy(bufs[b], c_off[rs], c_len[rs].astype(np.uint32), out, roff[rs] + HDR + klen[rs].astype(np.uint64),
-                  stream)
+            batch.copy_blocks(bufs[b], c_off[rs], c_len[rs], out, voff_out[rs])
     # crc field (records are 256-B aligned, so int32 words)
-    out.view(torch.int32)[torch.from_numpy((roff // 4).astype(np.int64)).to(dev)] = crc_d
+    out.view(torch.int32)[_dev.u64(roff // 4, dev)] = crc_d
     return Encoded(out[:total], roff, flags, vsz.astype(np.uint32), crc)
 
 
@@ -259,16 +251,9 @@ class EncodedBatch:
     counts: tuple[int, int, int, int] = (0, 0, 0, 0)   # OK records, ntry, nkeep, nfull (the two read-backs)
 
 
-def _dev_i32(a, n, dev, dtype=np.uint32):
-    if a is None:
-        return torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    if isinstance(a, torch.Tensor):
-        return a.to(device=dev, dtype=torch.int32).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype)).view(np.int32)).to(dev)
-
-
+@_dev.on_stream
 def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, vers=None, ts=None,
-                 not_compress=NOT_COMPRESS, max_key: int = 250, body_max: int = 50 << 20,
+                 not_compress=NOT_COMPRESS, max_key: int = MAX_KEY_LEN, body_max: int = BODY_MAX,
                  workspace: batch.Workspace | None = None, stream=None, out: torch.Tensor | None = None,
                  out_cap: int | None = None) -> EncodedBatch:
     """TryCompress + encodeHeader + padding for n records whose keys and values live on the device
@@ -276,10 +261,6 @@ def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, v
     Sizes, flags, offsets and CRCs stay on the device; the host reads back the plan's and the
     decision's totals only, to size the compress launches and the buffers.  `out` / `out_cap`
     (optional) give the destination and the bytes of it that may be written."""
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            return encode_batch(keys, values, flags, vers, ts, not_compress, max_key, body_max, workspace,
-                                None, out, out_cap)
     L = _lib.lib()
     dev = values.data.device
     n = values.n
@@ -288,7 +269,8 @@ def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, v
     ws = workspace or batch.Workspace(dev)
     st_ = batch._stream()
     cap = max(n, 1)
-    flags, vers, ts = _dev_i32(flags, n, dev), _dev_i32(vers, n, dev, np.int32), _dev_i32(ts, n, dev)
+    flags, vers, ts = (torch.zeros(cap, dtype=torch.int32, device=dev) if a is None else _dev.i32(a, dev)
+                       for a in (flags, vers, ts))
     i32 = lambda k=cap: torch.empty(k, dtype=torch.int32, device=dev)   # noqa: E731
     i64 = lambda k=cap: torch.empty(k, dtype=torch.int64, device=dev)   # noqa: E731
     status, try_idx, try_off, try_len, try_dst = i32(), i32(), i64(), i32(), i64()
@@ -300,9 +282,9 @@ def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, v
                                  not_compress_mask(not_compress), status.data_ptr(), try_idx.data_ptr(),
                                  try_off.data_ptr(), try_len.data_ptr(), try_dst.data_ptr(), totals.data_ptr(),
                                  wsp(), ws_bytes, st_), "qlzx_write_plan")
-    t = totals.cpu().numpy().view(np.uint32)          # read-back 1: sizes the trial compress
+    t = _dev.readback(totals)                              # read-back 1: sizes the trial compress
     nok, ntry, max_try = int(t[0]), int(t[1]), int(t[2])
-    trial_bytes, bound = int(t[3]) | (int(t[4]) << 32), int(t[5]) | (int(t[6]) << 32)
+    trial_bytes, bound = _dev.wide(t, 3), _dev.wide(t, 5)
     tbuf = tcs = tst = tcrc = None
     if ntry:
         tbuf = torch.empty(trial_bytes, dtype=torch.uint8, device=dev)
@@ -320,9 +302,9 @@ def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, v
                                    keep.data_ptr(), full_idx.data_ptr(), full_off.data_ptr(), full_len.data_ptr(),
                                    full_dst.data_ptr(), totals2.data_ptr(), wsp(), ws_bytes, st_),
                "qlzx_write_decide")
-    t2 = totals2.cpu().numpy().view(np.uint32)        # read-back 2: sizes the full compress
+    t2 = _dev.readback(totals2)                            # read-back 2: sizes the full compress
     nkeep, nfull, max_full = int(t2[0]), int(t2[1]), int(t2[2])
-    full_bytes = int(t2[3]) | (int(t2[4]) << 32)
+    full_bytes = _dev.wide(t2, 3)
     fbuf = None
     if nfull:
         fbuf = torch.empty(full_bytes, dtype=torch.uint8, device=dev)
@@ -343,45 +325,25 @@ def encode_batch(keys: batch.BlockBatch, values: batch.BlockBatch, flags=None, v
                                    keys.data.data_ptr(), keys.off.data_ptr(), keys.length.data_ptr(),
                                    flags.data_ptr(), vers.data_ptr(), ts.data_ptr(), n, totals.data_ptr(),
                                    try_idx.data_ptr(), try_len.data_ptr(), try_dst.data_ptr(), tcs.data_ptr(),
-                                   tcrc.data_ptr(), keep.data_ptr(), batch._ptr(tbuf), totals2.data_ptr(),
+                                   tcrc.data_ptr(), keep.data_ptr(), _dev.ptr(tbuf), totals2.data_ptr(),
                                    full_idx.data_ptr(), full_dst.data_ptr(), fcs.data_ptr(), fst.data_ptr(),
-                                   fcrc.data_ptr(), batch._ptr(fbuf), out.data_ptr(), out_cap, status.data_ptr(),
+                                   fcrc.data_ptr(), _dev.ptr(fbuf), out.data_ptr(), out_cap, status.data_ptr(),
                                    rec_off.data_ptr(), flag_out.data_ptr(), vsz.data_ptr(), crc.data_ptr(),
                                    vh16.data_ptr(), totals3.data_ptr(), wsp(), ws_bytes, st_), "qlzx_write_finish")
     return EncodedBatch(out, rec_off[:n], flag_out[:n], vsz[:n], crc[:n], status[:n],
                         vh16[:n].to(torch.int32) & 0xFFFF, totals3, try_idx[:ntry], (nok, ntry, nkeep, nfull))
 
 
-def _copy(src: torch.Tensor, src_off, length, dst: torch.Tensor, dst_off, stream=None):
-    L = _lib.lib()
-    n = len(src_off)
-    if n == 0:
-        return
-    dev = dst.device
-    so, ln, do = _dev_u64(src_off, dev), _dev_u32(length, dev), _dev_u64(dst_off, dev)
-    _lib.check(L.qlzx_copy_batch(src.data_ptr(), so.data_ptr(), ln.data_ptr(), dst.data_ptr(), do.data_ptr(), n,
-                                 batch._stream(stream)), "qlzx_copy_batch")
+_copy = batch.copy_blocks   # the name tools/bench_read.py calls
 
 
 def _gather_heads(values: batch.BlockBatch, idx: np.ndarray, k: int) -> np.ndarray:
     """The first k bytes of each selected value (zeros past its end), uint8 [len(idx), k]."""
     dev = values.data.device
-    sel = torch.from_numpy(idx).to(dev)
+    sel = _dev.u64(idx, dev)
     off = values.off[sel]
     ln = values.length[sel].to(torch.int64)
     ar = torch.arange(k, device=dev)
     pos = torch.minimum(off.unsqueeze(1) + ar.unsqueeze(0), torch.tensor(values.data.numel() - 1, device=dev))
     h = values.data[pos.reshape(-1)].reshape(len(idx), k)
     return torch.where(ar.unsqueeze(0) < ln.unsqueeze(1), h, torch.zeros_like(h)).cpu().numpy()
-
-
-def _gather_prefix(values: batch.BlockBatch, idx: np.ndarray, k: int) -> list[bytes]:
-    dev = values.data.device
-    off = values.off[torch.from_numpy(idx).to(dev)]
-    ln = values.length[torch.from_numpy(idx).to(dev)].to(torch.int64)
-    ar = torch.arange(k, device=dev)
-    pos = off.unsqueeze(1) + ar.unsqueeze(0)
-    pos = torch.minimum(pos, torch.tensor(values.data.numel() - 1, device=dev))
-    h = values.data[pos.reshape(-1)].reshape(len(idx), k).cpu().numpy()
-    lh = np.minimum(ln.cpu().numpy(), k)
-    return [h[j, : lh[j]].tobytes() for j in range(len(idx))]

@@ -16,12 +16,18 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, batch
+from . import _dev, _lib, batch
+from ._dev import on_stream, ptr
+from .record import BODY_MAX, FLAG_COMPRESS, HDR, MAX_KEY_LEN
 
-HDR = 24
-FLAG_COMPRESS = 0x00010000
-MAX_KEY_LEN = 250          # config/mc_config.go:6
-BODY_MAX = 50 << 20        # config/mc_config.go:7 ("50M")
+
+def _value(r, j: int) -> bytes:
+    """Entry j's value after Payload.Decompress (store/item.go:163-176), of a ReplayResult or a
+    ReadResult: the decoded bytes, or the raw body where the record is not compressed or its
+    decode failed."""
+    o, n = int(r.val_off[j]), int(r.value_len[j])
+    src = r.values.data if int(r.in_out[j]) else r.data
+    return src[o:o + n].cpu().numpy().tobytes()
 
 
 @dataclass
@@ -47,13 +53,9 @@ class ReplayResult:
     def n(self) -> int:
         return int(self.offset.numel())
 
-    def value(self, j: int) -> bytes:
-        """Record j's value after Payload.Decompress (store/item.go:163-176): the decoded bytes, or
-        the raw body where the record is not compressed or its decode failed."""
-        o, n = int(self.val_off[j]), int(self.value_len[j])
-        src = self.values.data if int(self.in_out[j]) else self.data
-        return src[o:o + n].cpu().numpy().tobytes()
+    value = _value
 
+    @on_stream
     def value_crcs(self, stream=None) -> torch.Tensor:
         """crc32 (store/crc32.go get) of every record's value after Payload.Decompress, on the
         device (int32 [n]); an XOR of them is the parity digest of a replay."""
@@ -61,13 +63,65 @@ class ReplayResult:
         for where, src in ((1, self.values.data), (0, self.data)):
             m = torch.nonzero(self.in_out == where).flatten()
             if m.numel():
-                out[m] = batch.crc32(batch.BlockBatch(src, self.val_off[m], self.value_len[m]), stream=stream)
+                out[m] = batch.crc32(batch.BlockBatch(src, self.val_off[m], self.value_len[m]))
         return out
 
 
-def index(data: torch.Tensor, start: int = 0, max_key: int = MAX_KEY_LEN, body_max: int = BODY_MAX,
-          workspace: batch.Workspace | None = None, stream=None):
-    """Records DataStreamReader.Next would return from `start`: (offsets, sizeBroken, end_error, ncand, nvalid)."""
+def _ptrs(tensors) -> list[int]:
+    return [t.data_ptr() for t in tensors]
+
+
+@dataclass
+class _Plan:
+    """What qlzx_replay_plan / qlzx_read_plan fill: the stored headers, and per FLAG_COMPRESS
+    record its entry, its body in the chunk, the dsize of its QuickLZ header and its place in the
+    decoder output; totals = (entries, compressed ones, largest dsize, output bytes lo, hi)."""
+    hdr: torch.Tensor
+    comp_idx: torch.Tensor
+    comp_off: torch.Tensor
+    comp_len: torch.Tensor
+    comp_dsize: torch.Tensor
+    comp_dst: torch.Tensor
+    totals: torch.Tensor
+
+    @classmethod
+    def alloc(cls, cap: int, dev) -> "_Plan":
+        def empty(dtype, k=cap):
+            return torch.empty(k, dtype=dtype, device=dev)
+        return cls(empty(torch.int32, cap * 6), empty(torch.int32), empty(torch.int64), empty(torch.int32),
+                   empty(torch.int32), empty(torch.int64), torch.zeros(5, dtype=torch.int32, device=dev))
+
+    def ptrs(self) -> list[int]:
+        """The addresses of the seven arrays, in the order both plan calls take them."""
+        return _ptrs((self.hdr, self.comp_idx, self.comp_off, self.comp_len, self.comp_dsize, self.comp_dst,
+                      self.totals))
+
+
+def _decode_planned(data: torch.Tensor, p: _Plan, cap: int, ws: batch.Workspace):
+    """The middle of replay() and read_records(), after the plan call: the one read-back (it sizes
+    the output buffer and the decoder launch) and the decode of the planned records.  Returns
+    (entries, compressed ones, largest dsize, output bytes), the decoder's output, what a finish
+    call reads of it (comp_idx, status, dsize, comp_dst, output: the order both take them in) and
+    the five arrays it fills (flag, value_len, in_out, val_off, vh16)."""
+    dev = data.device
+    t = _dev.readback(p.totals)
+    ncomp, maxd, out_bytes = int(t[1]), int(t[2]), _dev.wide(t, 3)
+    out = torch.empty(out_bytes + 64, dtype=torch.uint8, device=dev)
+    cst = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
+    cds = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
+    values = batch.BlockBatch(out, p.comp_dst[:ncomp], p.comp_dsize[:ncomp])
+    if ncomp:
+        csrc = batch.BlockBatch(data, p.comp_off[:ncomp], p.comp_len[:ncomp])
+        cds, cst, _ = batch.decompress(csrc, values, dst_cap=p.comp_dsize[:ncomp], max_dsize=maxd, workspace=ws)
+    decoded = [p.comp_idx, cst, cds, p.comp_dst, out]
+    fin = [torch.empty(cap, dtype=dt, device=dev)
+           for dt in (torch.int32, torch.int32, torch.uint8, torch.int64, torch.int16)]
+    return (int(t[0]), ncomp, maxd, out_bytes), values, decoded, fin
+
+
+def _index_device(data: torch.Tensor, start: int, max_key: int, body_max: int, ws: batch.Workspace):
+    """qlzx_replay_index launched on the current stream: (rec_off, rec_broken, result), all on the
+    device, with room for size // 256 + 1 records; result = (n, end_error, ncand, nvalid)."""
     L = _lib.lib()
     dev = data.device
     size = int(data.numel())
@@ -76,16 +130,24 @@ def index(data: torch.Tensor, start: int = 0, max_key: int = MAX_KEY_LEN, body_m
     rec_broken = torch.empty(cap, dtype=torch.int32, device=dev)
     result = torch.zeros(4, dtype=torch.int32, device=dev)
     ws_bytes = L.qlzx_replay_workspace_size(size)
-    ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
-    rc = L.qlzx_replay_index(data.data_ptr() if size else None, size, start, max_key, body_max,
-                             rec_off.data_ptr(), rec_broken.data_ptr(), result.data_ptr(), ws.data_ptr(),
-                             ws_bytes, batch._stream(stream))
-    _lib.check(rc, "qlzx_replay_index")
+    _lib.check(L.qlzx_replay_index(ptr(data), size, start, max_key, body_max, rec_off.data_ptr(),
+                                   rec_broken.data_ptr(), result.data_ptr(), ws.get(ws_bytes).data_ptr(), ws_bytes,
+                                   batch._stream()), "qlzx_replay_index")
+    return rec_off, rec_broken, result
+
+
+@on_stream
+def index(data: torch.Tensor, start: int = 0, max_key: int = MAX_KEY_LEN, body_max: int = BODY_MAX,
+          workspace: batch.Workspace | None = None, stream=None):
+    """Records DataStreamReader.Next would return from `start`: (offsets, sizeBroken, end_error, ncand, nvalid)."""
+    rec_off, rec_broken, result = _index_device(data, start, max_key, body_max,
+                                                workspace or batch.Workspace(data.device))
     r = result.cpu().numpy()
     n = int(r[0])
     return rec_off[:n], rec_broken[:n], bool(r[1]), int(r[2]), int(r[3])
 
 
+@on_stream
 def replay(data: torch.Tensor, start: int = 0, max_key: int = MAX_KEY_LEN, body_max: int = BODY_MAX,
            workspace: batch.Workspace | None = None, stream=None) -> ReplayResult:
     """Index, plan, decompress, finish: every per-record step runs on the device
@@ -95,94 +157,20 @@ def replay(data: torch.Tensor, start: int = 0, max_key: int = MAX_KEY_LEN, body_
     L = _lib.lib()
     dev = data.device
     ws = workspace or batch.Workspace(dev)
-    size = int(data.numel())
-    cap = size // 256 + 1
-    st_ = batch._stream(stream)
-    rec_off = torch.empty(cap, dtype=torch.int64, device=dev)
-    rec_broken = torch.empty(cap, dtype=torch.int32, device=dev)
-    result = torch.zeros(4, dtype=torch.int32, device=dev)
-    ws_bytes = L.qlzx_replay_workspace_size(size)
-    w = ws.get(ws_bytes)
-    _lib.check(L.qlzx_replay_index(data.data_ptr() if size else None, size, start, max_key, body_max,
-                                   rec_off.data_ptr(), rec_broken.data_ptr(), result.data_ptr(), w.data_ptr(),
-                                   ws_bytes, st_), "qlzx_replay_index")
-    hdr = torch.empty(cap * 6, dtype=torch.int32, device=dev)
-    comp_idx = torch.empty(cap, dtype=torch.int32, device=dev)
-    comp_off = torch.empty(cap, dtype=torch.int64, device=dev)
-    comp_len = torch.empty(cap, dtype=torch.int32, device=dev)
-    comp_dsize = torch.empty(cap, dtype=torch.int32, device=dev)
-    comp_dst = torch.empty(cap, dtype=torch.int64, device=dev)
-    totals = torch.zeros(5, dtype=torch.int32, device=dev)
+    st_ = batch._stream()
+    rec_off, rec_broken, result = _index_device(data, start, max_key, body_max, ws)
+    cap = int(rec_off.numel())
+    p = _Plan.alloc(cap, dev)
     pws = torch.empty(L.qlzx_replay_plan_workspace_size(cap), dtype=torch.uint8, device=dev)
-    _lib.check(L.qlzx_replay_plan(data.data_ptr() if size else None, rec_off.data_ptr(), result.data_ptr(), cap,
-                                  hdr.data_ptr(), comp_idx.data_ptr(), comp_off.data_ptr(), comp_len.data_ptr(),
-                                  comp_dsize.data_ptr(), comp_dst.data_ptr(), totals.data_ptr(), pws.data_ptr(),
+    _lib.check(L.qlzx_replay_plan(ptr(data), rec_off.data_ptr(), result.data_ptr(), cap, *p.ptrs(), pws.data_ptr(),
                                   pws.numel(), st_), "qlzx_replay_plan")
-    # the one read-back: it sizes the output buffer and the decoder launch
-    with torch.cuda.stream(stream) if stream is not None else _nullctx():
-        t = totals.cpu().numpy().view(np.uint32)
-        r = result.cpu().numpy()
-    n, ncomp, maxd = int(t[0]), int(t[1]), int(t[2])
-    out_bytes = int(t[3]) | (int(t[4]) << 32)
-    out = torch.empty(out_bytes + 64, dtype=torch.uint8, device=dev)
-    cst = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
-    cds = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
-    values = batch.BlockBatch(out, comp_dst[:ncomp], comp_dsize[:ncomp])
-    if ncomp:
-        csrc = batch.BlockBatch(data, comp_off[:ncomp], comp_len[:ncomp])
-        cds, cst, _ = batch.decompress(csrc, values, dst_cap=comp_dsize[:ncomp], max_dsize=maxd, workspace=ws,
-                                       stream=stream)
-    flag = torch.empty(cap, dtype=torch.int32, device=dev)
-    value_len = torch.empty(cap, dtype=torch.int32, device=dev)
-    in_out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    val_off = torch.empty(cap, dtype=torch.int64, device=dev)
-    vh16 = torch.empty(cap, dtype=torch.int16, device=dev)
-    _lib.check(L.qlzx_replay_finish(data.data_ptr() if size else None, rec_off.data_ptr(), result.data_ptr(),
-                                    totals.data_ptr(), comp_idx.data_ptr(), cst.data_ptr(), cds.data_ptr(),
-                                    comp_dst.data_ptr(), out.data_ptr(), cap, flag.data_ptr(), value_len.data_ptr(),
-                                    in_out.data_ptr(), val_off.data_ptr(), vh16.data_ptr(), st_),
-               "qlzx_replay_finish")
-    vh = vh16[:n].to(torch.int32) & 0xFFFF
-    return ReplayResult(rec_off[:n], rec_broken[:n], hdr[: 6 * n].view(n, 6), flag[:n], value_len[:n], vh, values,
-                        bool(r[1]), int(r[2]), int(r[3]), in_out[:n], val_off[:n], data)
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-def _headers_dsize(data: torch.Tensor, off: np.ndarray, length: np.ndarray) -> np.ndarray:
-    """Decompressed sizes from the QuickLZ headers (host parse of 9 bytes per block, quicklz.go:32-44);
-    0 where the body is too short to hold a header (the decoder reports it)."""
-    n = len(off)
-    if n == 0:
-        return np.zeros(0, np.uint32)
-    idx = torch.from_numpy(off.view(np.int64)).to(data.device).unsqueeze(1) + torch.arange(9, device=data.device)
-    idx = torch.clamp(idx, max=data.numel() - 1)
-    h = data[idx.reshape(-1)].reshape(n, 9).cpu().numpy()
-    big = (h[:, 0] & 2) != 0
-    d9 = h[:, 5].astype(np.uint32) | (h[:, 6].astype(np.uint32) << 8) | (h[:, 7].astype(np.uint32) << 16) | \
-        (h[:, 8].astype(np.uint32) << 24)
-    d3 = h[:, 2].astype(np.uint32)
-    d = np.where(big, d9, d3).astype(np.uint32)
-    d[length < np.where(big, 9, 3)] = 0
-    return np.minimum(d, BODY_MAX).astype(np.uint32)
-
-
-def _vhash(src: torch.Tensor, off: torch.Tensor, length: torch.Tensor, out16: torch.Tensor, where: torch.Tensor,
-           stream=None):
-    L = _lib.lib()
-    n = int(off.numel())
-    o = off.to(torch.int64).contiguous()
-    ln = length.to(torch.int32).contiguous()
-    tmp = torch.zeros(n, dtype=torch.int16, device=src.device)
-    rc = L.qlzx_vhash_batch(src.data_ptr(), o.data_ptr(), ln.data_ptr(), n, tmp.data_ptr(), batch._stream(stream))
-    _lib.check(rc, "qlzx_vhash_batch")
-    out16[where] = tmp
+    r = result.cpu().numpy()
+    (n, *_), values, decoded, fin = _decode_planned(data, p, cap, ws)
+    _lib.check(L.qlzx_replay_finish(ptr(data), rec_off.data_ptr(), result.data_ptr(), p.totals.data_ptr(),
+                                    *_ptrs(decoded), cap, *_ptrs(fin), st_), "qlzx_replay_finish")
+    flag, value_len, in_out, val_off, vh16 = (x[:n] for x in fin)
+    return ReplayResult(rec_off[:n], rec_broken[:n], p.hdr[: 6 * n].view(n, 6), flag, value_len,
+                        vh16.to(torch.int32) & 0xFFFF, values, bool(r[1]), int(r[2]), int(r[3]), in_out, val_off, data)
 
 
 @dataclass
@@ -434,11 +422,10 @@ class ReadResult:
         st = int(self.status[i])
         if st != _lib.RD_OK:
             raise ValueError(f"request {i} failed: {_lib.RD_NAMES[st]}")
-        o, n = int(self.val_off[i]), int(self.value_len[i])
-        src = self.values.data if int(self.in_out[i]) else self.data
-        return src[o:o + n].cpu().numpy().tobytes()
+        return _value(self, i)
 
 
+@on_stream
 def read_records(data: torch.Tensor, offsets, keys: list[bytes] | None = None, max_key: int = MAX_KEY_LEN,
                  body_max: int = BODY_MAX, workspace: batch.Workspace | None = None, stream=None) -> ReadResult:
     """Many records at positions the caller knows, in one pass (a multi-key GET, GC's collision
@@ -450,74 +437,38 @@ def read_records(data: torch.Tensor, offsets, keys: list[bytes] | None = None, m
     the record CRC was verified before any QuickLZ header was believed); qlzx_read_finish reports
     per request.  `keys` (optional, one per offset) are compared on the device: key_eq[i] == 0 on
     an OK request is the caller's hash collision (store/bucket.go:452-498), not an error."""
-    if stream is not None:   # uploads, launches and the read-back all on the caller's stream
-        with torch.cuda.stream(stream):
-            return read_records(data, offsets, keys, max_key, body_max, workspace)
     L = _lib.lib()
     dev = data.device
     ws = workspace or batch.Workspace(dev)
     st_ = batch._stream()
     size = int(data.numel())
-    if isinstance(offsets, torch.Tensor):
-        off = offsets.to(device=dev, dtype=torch.int64).contiguous()
-    else:
-        host = np.asarray(offsets)
-        host = host.view(np.int64) if host.dtype == np.uint64 else host.astype(np.int64)
-        off = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).to(dev)
+    off = _dev.u64(offsets, dev).reshape(-1)
     n = int(off.numel())
     cap = max(n, 1)
     wk = wk_off = wk_len = key_eq = None
     if keys is not None:
         if len(keys) != n:
             raise ValueError("keys: one per offset")
-        koff, _ = batch.pack_offsets([len(k) for k in keys], align=1)
+        klen = np.fromiter(map(len, keys), np.int32, count=n)
+        koff, _ = batch.pack_offsets(klen, align=1)
         wk = torch.from_numpy(np.frombuffer(b"".join(keys) + b"\0", dtype=np.uint8).copy()).to(dev)
-        wk_off = torch.from_numpy(koff.view(np.int64)).to(dev)     # (null pointers when n == 0: not read)
-        wk_len = torch.from_numpy(np.asarray([len(k) for k in keys], dtype=np.int32)).to(dev)
+        wk_off, wk_len = _dev.u64(koff, dev), _dev.i32(klen, dev)     # (null pointers when n == 0: not read)
         key_eq = torch.empty(cap, dtype=torch.uint8, device=dev)
     if n == 0:
         off = torch.zeros(1, dtype=torch.int64, device=dev)
     status = torch.empty(cap, dtype=torch.int32, device=dev)
-    hdr = torch.empty(cap * 6, dtype=torch.int32, device=dev)
-    comp_idx = torch.empty(cap, dtype=torch.int32, device=dev)
-    comp_off = torch.empty(cap, dtype=torch.int64, device=dev)
-    comp_len = torch.empty(cap, dtype=torch.int32, device=dev)
-    comp_dsize = torch.empty(cap, dtype=torch.int32, device=dev)
-    comp_dst = torch.empty(cap, dtype=torch.int64, device=dev)
-    totals = torch.zeros(5, dtype=torch.int32, device=dev)
+    p = _Plan.alloc(cap, dev)
     ws_bytes = L.qlzx_read_plan_workspace_size(n)
-    w = ws.get(ws_bytes)
-    _lib.check(L.qlzx_read_plan(data.data_ptr() if size else None, size, off.data_ptr(), n, max_key, body_max,
-                                batch._ptr(wk), batch._ptr(wk_off), batch._ptr(wk_len), status.data_ptr(),
-                                batch._ptr(key_eq), hdr.data_ptr(), comp_idx.data_ptr(), comp_off.data_ptr(),
-                                comp_len.data_ptr(), comp_dsize.data_ptr(), comp_dst.data_ptr(), totals.data_ptr(),
-                                w.data_ptr(), ws_bytes, st_), "qlzx_read_plan")
-    # the one read-back: it sizes the output buffer and the decoder launch
-    t = totals.cpu().numpy().view(np.uint32)
-    ncomp, maxd = int(t[1]), int(t[2])
-    out_bytes = int(t[3]) | (int(t[4]) << 32)
-    out = torch.empty(out_bytes + 64, dtype=torch.uint8, device=dev)
-    cst = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
-    cds = torch.zeros(max(ncomp, 1), dtype=torch.int32, device=dev)
-    values = batch.BlockBatch(out, comp_dst[:ncomp], comp_dsize[:ncomp])
-    if ncomp:
-        csrc = batch.BlockBatch(data, comp_off[:ncomp], comp_len[:ncomp])
-        cds, cst, _ = batch.decompress(csrc, values, dst_cap=comp_dsize[:ncomp], max_dsize=maxd, workspace=ws)
-    flag = torch.empty(cap, dtype=torch.int32, device=dev)
-    value_len = torch.empty(cap, dtype=torch.int32, device=dev)
-    in_out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    val_off = torch.empty(cap, dtype=torch.int64, device=dev)
-    vh16 = torch.empty(cap, dtype=torch.int16, device=dev)
+    _lib.check(L.qlzx_read_plan(ptr(data), size, off.data_ptr(), n, max_key, body_max, ptr(wk), ptr(wk_off),
+                                ptr(wk_len), status.data_ptr(), ptr(key_eq), *p.ptrs(), ws.get(ws_bytes).data_ptr(),
+                                ws_bytes, st_), "qlzx_read_plan")
+    t, values, decoded, fin = _decode_planned(data, p, cap, ws)
     dec = torch.empty(cap, dtype=torch.int32, device=dev)
-    _lib.check(L.qlzx_read_finish(data.data_ptr() if size else None, off.data_ptr(), n, status.data_ptr(),
-                                  totals.data_ptr(), comp_idx.data_ptr(), cst.data_ptr(), cds.data_ptr(),
-                                  comp_dst.data_ptr(), out.data_ptr(), flag.data_ptr(), value_len.data_ptr(),
-                                  in_out.data_ptr(), val_off.data_ptr(), vh16.data_ptr(), dec.data_ptr(), st_),
-               "qlzx_read_finish")
-    vh = vh16[:n].to(torch.int32) & 0xFFFF
-    return ReadResult(status[:n], None if key_eq is None else key_eq[:n], hdr[: 6 * n].view(n, 6), flag[:n],
-                      value_len[:n], vh, dec[:n], in_out[:n], val_off[:n], values, data,
-                      (int(t[0]), ncomp, maxd, out_bytes))
+    _lib.check(L.qlzx_read_finish(ptr(data), off.data_ptr(), n, status.data_ptr(), p.totals.data_ptr(),
+                                  *_ptrs(decoded), *_ptrs(fin), dec.data_ptr(), st_), "qlzx_read_finish")
+    flag, value_len, in_out, val_off, vh16 = (x[:n] for x in fin)
+    return ReadResult(status[:n], None if key_eq is None else key_eq[:n], p.hdr[: 6 * n].view(n, 6), flag, value_len,
+                      vh16.to(torch.int32) & 0xFFFF, dec[:n], in_out, val_off, values, data, t)
 
 
 def read_record(rec: bytes) -> tuple[int, bytes] | None:

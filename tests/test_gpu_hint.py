@@ -135,6 +135,12 @@ def test_duplicates_keep_the_last_version(cuda):
     keys = tuple(rnd.choice(names) for _ in range(300))
     res, recs, got = _build(cuda, _chunk(keys, seed=9))
     assert len(got) == 1 and got[0].num_key == 7
+    import torch
+    from gobeansdb_amd import hint
+    side = torch.cuda.Stream()   # the same call on a stream of the caller's: the same file bytes
+    on_side = hint.build(res, stream=side)
+    side.synchronize()
+    assert len(on_side) == 1 and torch.equal(on_side[0].file, got[0].file)
     last = {r[1]: r for r in recs}
     items = H.read_items(got[0].file.cpu().numpy().tobytes())
     assert sorted((i.key, i.offset, i.ver, i.vhash) for i in items) == \

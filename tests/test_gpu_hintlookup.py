@@ -449,9 +449,14 @@ def test_from_key_to_value_on_the_device(cuda):
     kb = batch.BlockBatch.from_bytes(distinct, device=cuda)
     layouts = [([sp.file for sp in splits[::-1]], [6] * 3, None),   # splits only, newest first
                ([merged.file], [0], 0)]                             # the merged file alone
+    side = torch.cuda.Stream()
     for files, chunks, mg in layouts:
         res = hint.lookup(files, chunks, kb, merged=mg, bounded=True)
         assert res.totals == (len(distinct), 0, 0, 0)
+        on_side = hint.lookup(files, chunks, kb, merged=mg, bounded=True, stream=side)   # a stream of the caller's
+        side.synchronize()
+        assert on_side.totals == res.totals and torch.equal(on_side.status, res.status)
+        assert torch.equal(on_side.chunk, res.chunk) and torch.equal(on_side.offset, res.offset)
         assert res.status.cpu().tolist() == [_lib.HL_FOUND] * len(distinct)
         assert res.chunk.cpu().tolist() == [6] * len(distinct)
         offsets = res.offset.to(torch.int64) & 0xFFFFFFFF

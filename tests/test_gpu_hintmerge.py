@@ -109,7 +109,15 @@ def test_offsets_from_2_31_compare_unsigned(cuda):
 def test_chunk_ids_in_any_order(cuda, order):
     files = _sources(7, 65, 31)
     chunks = [60, 50, 40, 30, 20, 10, 0] if order == "descending" else [3, 0xFFFFFFFE, 0, 7, 3, 1, 0x80000000]
-    _merge(cuda, files, chunks, index_interval=279)
+    got, _ = _merge(cuda, files, chunks, index_interval=279)
+    import torch
+    from gobeansdb_amd import hint
+    on_dev = [_dev(f, cuda) for f in files]
+    torch.cuda.synchronize()     # the uploads ran on the default stream
+    side = torch.cuda.Stream()   # the same call on a stream of the caller's: the same file bytes
+    on_side = hint.merge(on_dev, chunks, index_interval=279, stream=side)
+    side.synchronize()
+    assert torch.equal(on_side.file, got.file) and on_side.num_key == got.num_key
 
 
 # ---- keys ----

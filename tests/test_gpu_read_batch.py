@@ -330,6 +330,14 @@ def test_agrees_with_replay_and_read_record(cuda):
     side.synchronize()
     assert torch.equal(on_side.vhash, rd.vhash) and torch.equal(on_side.val_off, rd.val_off)
     assert int(on_side.key_eq.sum()) == 0 and [on_side.value(j) for j in (0, 39)] == [rd.value(0), rd.value(39)]
+    rp_side = replay.replay(t, stream=side)
+    side.synchronize()
+    for name in ("offset", "header", "flag", "value_len", "vhash", "in_out", "val_off"):
+        assert torch.equal(getattr(rp_side, name), getattr(rp, name)), name
+    assert [rp_side.value(j) for j in (0, 39)] == [rp.value(0), rp.value(39)]
+    none = replay.replay(_dev(b""), stream=side)   # the empty chunk, zero bytes
+    side.synchronize()
+    assert none.n == 0 and not none.end_error and none.values.n == 0
     for j in range(0, 40, 5):
         ksz, vsz = int(rd.header[j, 4]), int(rd.header[j, 5])
         one = replay.read_record(data[offs[j]: offs[j] + 24 + ksz + vsz])
