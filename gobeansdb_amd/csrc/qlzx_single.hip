@@ -363,6 +363,12 @@ size_t qlzx_go_decompress1(const char *source, size_t source_len, void *destinat
     }
     const size_t hdr = (source[0] & 2) ? 9 : 3;
     const size_t dsize = source_len >= hdr ? qlz_size_decompressed(source) : 0;  // else the kernel: E_HEADER
+    const int level = ((unsigned char)source[0] >> 2) & 3;
+    if (source_len >= hdr && level != 1 && level != 3) {  // the kernel's order: header, level, then dst_cap
+        t_last_status = QLZX_E_LEVEL;
+        fail(QLZX_R_OK, "qlzx_go_decompress1: status 3");
+        return QLZX_GO_ERROR;
+    }
     if (dsize > dst_cap) {
         t_last_status = QLZX_E_DST_CAP;
         fail(QLZX_R_BAD_ARG, "qlzx_go_decompress1: destination too small");

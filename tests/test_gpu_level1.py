@@ -27,9 +27,13 @@ def l1():
 
 def _decode_batch(streams, caps):
     import torch
-    from gobeansdb_amd import batch
+    from gobeansdb_amd import _dev, batch
     src = batch.BlockBatch.from_bytes(streams)
-    out = batch.BlockBatch.empty_for([max(c, 1) for c in caps])
+    # a destination that holds 0xA5: Go's make([]byte, size) zero-fill is the decoder's to do
+    rooms = [max(c, 1) for c in caps]
+    off, total = batch.pack_offsets(rooms)
+    out = batch.BlockBatch(torch.full((max(total, 1),), 0xA5, dtype=torch.uint8, device="cuda"),
+                           _dev.u64(off, "cuda"), _dev.u32(rooms, "cuda"))
     cap_t = torch.tensor(np.asarray(caps, np.uint32).view(np.int32), device="cuda")
     dsize, st = batch.go_decompress(src, out, dst_cap=cap_t)
     torch.cuda.synchronize()
