@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("QLZX_LIB", os.path.join(HERE, "libqlzx.so"))
 HEADER = os.path.join(ROOT, "include", "qlzx.h")
+HTREE_HEADER = os.path.join(ROOT, "include", "qlzx_htree.h")
 
 # enum qlzx_status
 OK, E_SIZE_COMPRESSED, E_CORRUPT, E_LEVEL, E_DST_CAP, E_CRC, E_HEADER, E_EMPTY, E_TOO_LARGE, E_MAX_DSIZE, E_RUNTIME = range(11)
@@ -49,6 +50,15 @@ HL_N_FOUND, HL_N_MISS, HL_N_ERR, HL_N_BAD_FILE = range(4)
 HL_FILE_MERGED = 1
 HL_F_BOUNDED, HL_F_LANE, HL_F_WAVE = 1, 2, 4
 HL_LANE_FROM = 16384            # QLZX_HL_LANE_FROM: a lane per request from this many on
+# qlzx_htree_plan / qlzx_htree_write (include/qlzx_htree.h): enum qlzx_ht_status (totals[8]), the
+# entries of totals[10], and what store/config.go:12 and store/htree.go:15-18 fix
+HT_OK, HT_NO_SPACE, HT_BAD_FILE, HT_TOO_MANY = range(4)
+HT_NAMES = ["HT_OK", "HT_NO_SPACE", "HT_BAD_FILE", "HT_TOO_MANY"]
+HT_OPS_READ, HT_N_SET, HT_N_REMOVE, HT_N_SLOTS, HT_N_LEAF, HT_BYTES_LO, HT_BYTES_HI, HT_STATUS_SOURCE, \
+    HT_STATUS = range(9)
+HT_KHASH_LENS = (8, 8, 7, 7, 6, 6, 5, 5)
+HT_MAX_DEPTH, HT_MAX_HEIGHT = 2, 6
+HT_LIST_THRESHOLD = 256         # thresholdListKey: a node with fewer items lists them
 MAX_NUM_CHUNK = 998  # store/data.go:15: the most destination chunks qlzx_gc_plan takes
 # QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
 # order, and one for every other answer
@@ -76,9 +86,9 @@ class Blocks(ctypes.Structure):
 _lib = None
 
 
-def header_functions() -> list[str]:
-    """Every function declared in include/qlzx.h."""
-    text = open(HEADER).read()
+def header_functions(header: str = HEADER) -> list[str]:
+    """Every function declared in include/qlzx.h (or in another header of the ABI)."""
+    text = open(header).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"^\s*#.*$", "", text, flags=re.M)   # preprocessor lines (#define X (...))
     return sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
@@ -181,6 +191,12 @@ def lib() -> ctypes.CDLL:
     L.qlzx_hint_lookup_workspace_size.restype = sz
     L.qlzx_hint_lookup.argtypes = [vp, u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32] + [vp] * 9 + [sz, vp]
     L.qlzx_hint_lookup.restype = ctypes.c_int
+    L.qlzx_htree_workspace_size.argtypes = [u64, u32, u32, u32]
+    L.qlzx_htree_workspace_size.restype = sz
+    L.qlzx_htree_plan.argtypes = [vp, u64, vp, vp, vp, u32, u32, u32, u32] + [vp] * 7 + [sz, vp]
+    L.qlzx_htree_plan.restype = ctypes.c_int
+    L.qlzx_htree_write.argtypes = [vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.qlzx_htree_write.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

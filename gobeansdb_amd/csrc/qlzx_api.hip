@@ -11,8 +11,9 @@
 // Unity build: the kernel sources are included here so the device tables
 // (qlzx_tables.hip) link without relocatable device code.  The five record-file sources
 // (replay, read, write, gc, hint) share qlzx_recfile.h; read also uses replay's k_rp_crc_long,
-// ScatterComp and finish kernels.  The three hint sources (hint, hintmerge, hintlookup) share
-// qlzx_hint_fmt.h, which each includes itself: their order here does not matter.
+// ScatterComp and finish kernels.  The four hint sources (hint, hintmerge, hintlookup, htree) share
+// qlzx_hint_fmt.h, hintmerge and htree also qlzx_hint_walk.h; each includes what it uses itself:
+// their order here does not matter.  htree's entry points are declared in include/qlzx_htree.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +41,7 @@
 #include "qlzx_hint.hip"
 #include "qlzx_hintmerge.hip"
 #include "qlzx_hintlookup.hip"
+#include "qlzx_htree.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -598,6 +600,51 @@ int qlzx_hint_lookup(const uint8_t *hints, uint64_t bytes, const uint64_t *file_
     const qlzx::HlOut out{status, hit_file, chunk, offset, ver, vhash, item_src, totals};
     const bool lane = flags & shapes ? (flags & QLZX_HL_F_LANE) != 0 : n >= QLZX_HL_LANE_FROM;
     return launched("qlzx_hint_lookup", qlzx::launch_hl(in, lane, out, workspace, (hipStream_t)stream));
+}
+
+size_t qlzx_htree_workspace_size(uint64_t bytes, uint32_t n_files, uint32_t cap, uint32_t height) {
+    (void)bytes, (void)height;
+    return qlzx::ht_ws_layout(n_files, cap, nullptr, nullptr);
+}
+
+int qlzx_htree_plan(const uint8_t *hints, uint64_t bytes, const uint64_t *file_off, const uint64_t *file_len,
+                    const uint32_t *file_chunk, uint32_t n_files, uint32_t cap, uint32_t depth, uint32_t height,
+                    uint32_t *node_count, uint16_t *node_hash, uint32_t *leaf_first, uint64_t *slot_src,
+                    uint32_t *slot_chunk, uint32_t *totals, void *workspace, size_t workspace_bytes, void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    qlzx::HtGeo g;
+    if (!qlzx::ht_geo(depth, height, &g))
+        return fail(QLZX_R_BAD_ARG, "qlzx_htree_plan: depth is 0..2 and height 1..6");
+    // no source is an empty tree: then the three per-source arrays may be null
+    if ((!hints && bytes) || (n_files && (!file_off || !file_len || !file_chunk)) || !node_count ||
+        !node_hash || !leaf_first || !slot_src || !slot_chunk || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_htree_plan: null arg");
+    if (int r = check_workspace("qlzx_htree_plan", workspace, workspace_bytes,
+                                qlzx_htree_workspace_size(bytes, n_files, cap, height)))
+        return r;
+    const qlzx::HmIn in{hints, bytes, file_off, file_len, file_chunk, n_files, cap};
+    return launched("qlzx_htree_plan", qlzx::launch_ht_plan(in, g, node_count, node_hash, leaf_first, slot_src,
+                    slot_chunk, totals, workspace, (hipStream_t)stream));
+}
+
+int qlzx_htree_write(const uint8_t *hints, uint64_t bytes, uint32_t cap, uint32_t depth, uint32_t height,
+                     const uint32_t *node_count, const uint16_t *node_hash, const uint32_t *leaf_first,
+                     const uint64_t *slot_src, const uint32_t *slot_chunk, uint8_t *out, uint64_t out_cap,
+                     uint32_t *totals, void *workspace, size_t workspace_bytes, void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    qlzx::HtGeo g;
+    if (!qlzx::ht_geo(depth, height, &g))
+        return fail(QLZX_R_BAD_ARG, "qlzx_htree_write: depth is 0..2 and height 1..6");
+    if ((!hints && bytes) || !node_count || !node_hash || !leaf_first || !slot_src || !slot_chunk ||
+        (!out && out_cap) || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_htree_write: null arg");
+    if ((uintptr_t)out & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_htree_write: out is not 16-B aligned");
+    // the plan's workspace, of a plan without a source at the least (the write itself keeps nothing in it)
+    if (int r = check_workspace("qlzx_htree_write", workspace, workspace_bytes,
+                                qlzx_htree_workspace_size(bytes, 0, cap, height)))
+        return r;
+    const qlzx::HtFile f{hints, bytes, node_count, node_hash, leaf_first, slot_src, slot_chunk};
+    return launched("qlzx_htree_write", qlzx::launch_ht_write(f, g, cap, out, out_cap, totals, (hipStream_t)stream));
 }
 
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,

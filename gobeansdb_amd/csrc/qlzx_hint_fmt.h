@@ -1,5 +1,6 @@
 // qlzx_hint_fmt.h -- what the hint-file kernels share (qlzx_hint.hip, qlzx_hintmerge.hip,
-// qlzx_hintlookup.hip; each includes this header itself): the hint file's format (head, item and
+// qlzx_hintlookup.hip, qlzx_htree.hip; each includes this header itself, the merge and the tree
+// through qlzx_hint_walk.h): the hint file's format (head, item and
 // index entry, store/hintfile.go:19-212) with its unaligned loads and hintFileReader.next's rule
 // stated once, getKeyHashDefalut and the key order, the counters and the (bytes, items) pair of a
 // plan, the sort's workspace tail with its scan, the run / fix kernels over any source of keys K,

@@ -22,8 +22,8 @@ the order getItem reaches them and a batch of keys, and returns per key where it
 index).  Every step runs in libqlzx.so (qlzx_hint_lookup, csrc/qlzx_hintlookup.hip); the results
 stay on the device (they feed replay.read_records / qlzx_read_plan), the host reads back totals[4].
 
-CollisionTable.compareAndSet against an existing table, the HTree and the in-memory
-HintBuffer.Get stay out of scope; the caller owns the files' bytes.
+The HTree built from those files is htree.py's.  CollisionTable.compareAndSet against an existing
+table and the in-memory HintBuffer.Get stay out of scope; the caller owns the files' bytes.
 """
 from __future__ import annotations
 
