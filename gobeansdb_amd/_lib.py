@@ -16,6 +16,7 @@ ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("QLZX_LIB", os.path.join(HERE, "libqlzx.so"))
 HEADER = os.path.join(ROOT, "include", "qlzx.h")
 HTREE_HEADER = os.path.join(ROOT, "include", "qlzx_htree.h")
+HTREE_GET_HEADER = os.path.join(ROOT, "include", "qlzx_htree_get.h")
 
 # enum qlzx_status
 OK, E_SIZE_COMPRESSED, E_CORRUPT, E_LEVEL, E_DST_CAP, E_CRC, E_HEADER, E_EMPTY, E_TOO_LARGE, E_MAX_DSIZE, E_RUNTIME = range(11)
@@ -59,6 +60,25 @@ HT_OPS_READ, HT_N_SET, HT_N_REMOVE, HT_N_SLOTS, HT_N_LEAF, HT_BYTES_LO, HT_BYTES
 HT_KHASH_LENS = (8, 8, 7, 7, 6, 6, 5, 5)
 HT_MAX_DEPTH, HT_MAX_HEIGHT = 2, 6
 HT_LIST_THRESHOLD = 256         # thresholdListKey: a node with fewer items lists them
+# include/qlzx_htree_get.h: enum qlzx_htg_status (qlzx_htree_get's verdict per key) and its
+# totals[2]; enum qlzx_htg_file and the entries of qlzx_htree_index's totals[4]; the get's flags
+HTG_MISS, HTG_FOUND = range(2)
+HTG_NAMES = ["HTG_MISS", "HTG_FOUND"]
+HTG_N_FOUND, HTG_N_MISS = range(2)
+HTG_OK, HTG_BAD_FILE = range(2)
+HTG_ITEMS, HTG_N_LEAF, HTG_STATUS, HTG_STATUS_LEAF = range(4)
+HTG_F_LANE, HTG_F_WAVE = 1, 2
+HTG_LANE_FROM = 4096            # QLZX_HTG_LANE_FROM: a lane per key from this many keys on ...
+HTG_LANE_LEAF = 64              # QLZX_HTG_LANE_LEAF: ... where the image holds at most this many items per leaf
+HTG_LANE_PER_ITEM = 256         # QLZX_HTG_LANE_PER_ITEM: ... and from this many keys per item of a leaf on
+HTG_NO_SLOT = 0xFFFFFFFF
+# enum qlzx_gl_verdict (qlzx_gc_liveness's verdict per record), the entries of its totals[8], its flag
+GL_BAD, GL_NEWEST, GL_OTHER_POS, GL_NOT_IN_TREE = range(4)
+GL_NAMES = ["GL_BAD", "GL_NEWEST", "GL_OTHER_POS", "GL_NOT_IN_TREE"]
+GL_N_RECORDS, GL_N_NEWEST, GL_N_OTHER_POS, GL_N_OTHER_POS_DELETED, GL_N_NOT_IN_TREE, GL_N_NOT_IN_TREE_KEPT, \
+    GL_N_BAD, GL_N_KEEP = range(8)
+GL_F_BEGIN_GT_0 = 1
+HTM_MOVED, HTM_SKIPPED = range(2)   # qlzx_htree_move's totals[2]
 MAX_NUM_CHUNK = 998  # store/data.go:15: the most destination chunks qlzx_gc_plan takes
 # QLZX_NC_*: one bit per audio/video row of http.DetectContentType's table, in record._AV_SIGS
 # order, and one for every other answer
@@ -197,6 +217,23 @@ def lib() -> ctypes.CDLL:
     L.qlzx_htree_plan.restype = ctypes.c_int
     L.qlzx_htree_write.argtypes = [vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp, sz, vp]
     L.qlzx_htree_write.restype = ctypes.c_int
+    L.qlzx_htree_index_workspace_size.argtypes = [u32]
+    L.qlzx_htree_index_workspace_size.restype = sz
+    L.qlzx_htree_index.argtypes = [vp, u64, u32, u32, vp, vp, vp, sz, vp]
+    L.qlzx_htree_index.restype = ctypes.c_int
+    L.qlzx_htree_get_workspace_size.argtypes = [u32]
+    L.qlzx_htree_get_workspace_size.restype = sz
+    L.qlzx_htree_get.argtypes = [vp, u64, vp, u32, u32, vp, vp, vp, vp, u32, u32] + [vp] * 8 + [sz, vp]
+    L.qlzx_htree_get.restype = ctypes.c_int
+    L.qlzx_gc_liveness_workspace_size.argtypes = [u32]
+    L.qlzx_gc_liveness_workspace_size.restype = sz
+    L.qlzx_gc_liveness.argtypes = [vp, u64, vp, vp, u32, u32, u64, u32, vp, u64, vp, u32, u32, vp, u32] + [vp] * 8 + \
+        [sz, vp]
+    L.qlzx_gc_liveness.restype = ctypes.c_int
+    L.qlzx_htree_move_workspace_size.argtypes = [u32]
+    L.qlzx_htree_move_workspace_size.restype = sz
+    L.qlzx_htree_move.argtypes = [vp, u64, vp, u32, u32, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, sz, vp]
+    L.qlzx_htree_move.restype = ctypes.c_int
     L.qlzx_vhash_batch.argtypes = [vp, vp, vp, u32, vp, vp]
     L.qlzx_vhash_batch.restype = ctypes.c_int
     L.qlzx_last_status.argtypes = []

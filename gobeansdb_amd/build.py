@@ -15,7 +15,8 @@ ARCH = os.environ.get("QLZX_ARCH", "gfx950")
 
 
 def source_hash() -> str:
-    """sha256 (first 16 hex digits) of every csrc/* file, include/qlzx.h, include/qlzx_htree.h and this build script
+    """sha256 (first 16 hex digits) of every csrc/* file, include/qlzx.h, include/qlzx_htree.h,
+    include/qlzx_htree_get.h and this build script
     (its compile flags and scheduler strategy), by name and content, plus the target
     arch: compiled into the library (qlzx_info: "src <hash>"), so a binary is tied to the sources
     and the way they were compiled."""
@@ -23,6 +24,7 @@ def source_hash() -> str:
     h.update(("arch=" + ARCH + "\0").encode())
     srcs = sorted(glob.glob(os.path.join(CSRC, "*"))) + [os.path.join(ROOT, "include", "qlzx.h"),
                                                          os.path.join(ROOT, "include", "qlzx_htree.h"),
+                                                         os.path.join(ROOT, "include", "qlzx_htree_get.h"),
                                                          os.path.abspath(__file__)]
     for s in srcs:
         if os.path.isfile(s):

@@ -14,6 +14,8 @@
 // ScatterComp and finish kernels.  The four hint sources (hint, hintmerge, hintlookup, htree) share
 // qlzx_hint_fmt.h, hintmerge and htree also qlzx_hint_walk.h; each includes what it uses itself:
 // their order here does not matter.  htree's entry points are declared in include/qlzx_htree.h.
+// htree_get (the queries over a built tree, include/qlzx_htree_get.h) uses htree's HtGeo and
+// comes after it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +44,7 @@
 #include "qlzx_hintmerge.hip"
 #include "qlzx_hintlookup.hip"
 #include "qlzx_htree.hip"
+#include "qlzx_htree_get.hip"
 #include "qlzx_record.hip"
 #include "qlzx_level1.hip"
 #include "qlzx_host.h"
@@ -645,6 +648,108 @@ int qlzx_htree_write(const uint8_t *hints, uint64_t bytes, uint32_t cap, uint32_
         return r;
     const qlzx::HtFile f{hints, bytes, node_count, node_hash, leaf_first, slot_src, slot_chunk};
     return launched("qlzx_htree_write", qlzx::launch_ht_write(f, g, cap, out, out_cap, totals, (hipStream_t)stream));
+}
+
+// ---- include/qlzx_htree_get.h ----
+// the tree every call takes: geometry, a non-null 16-B aligned image (unless empty) below 2^36 bytes
+static int check_htg_tree(const char *who, const void *image, uint64_t bytes, uint32_t depth, uint32_t height,
+                          qlzx::HtGeo *g) {
+    if (!qlzx::ht_geo(depth, height, g)) return fail_in(QLZX_R_BAD_ARG, who, "depth is 0..2 and height 1..6");
+    if (!image && bytes) return fail_in(QLZX_R_BAD_ARG, who, "null arg");
+    if ((uintptr_t)image & 15u) return fail_in(QLZX_R_BAD_ARG, who, "image is not 16-B aligned");
+    if (bytes >> 36) return fail_in(QLZX_R_BAD_ARG, who, "image of 2^36 bytes or more");
+    return QLZX_R_OK;
+}
+static int htg_shape(const char *who, uint32_t flags, uint32_t n, uint64_t bytes, const qlzx::HtGeo &g, bool *lane) {
+    constexpr uint32_t shapes = QLZX_HTG_F_LANE | QLZX_HTG_F_WAVE;
+    if ((flags & ~shapes) || (flags & shapes) == shapes)
+        return fail_in(QLZX_R_BAD_ARG, who, "unknown flag, or both kernels named");
+    *lane = flags & shapes ? (flags & QLZX_HTG_F_LANE) != 0 : qlzx::htg_lane_shape(n, bytes, g);
+    return QLZX_R_OK;
+}
+
+size_t qlzx_htree_index_workspace_size(uint32_t height) {
+    qlzx::HtGeo g;
+    return qlzx::ht_geo(0, height, &g) ? qlzx::hti_ws_layout(g.nleaf, nullptr, nullptr) : 0;
+}
+
+int qlzx_htree_index(const uint8_t *image, uint64_t bytes, uint32_t depth, uint32_t height, uint32_t *leaf_first,
+                     uint32_t *totals, void *workspace, size_t workspace_bytes, void *stream) {
+    qlzx::HtGeo g;
+    if (int r = check_htg_tree("qlzx_htree_index", image, bytes, depth, height, &g)) return r;
+    if (!leaf_first || !totals) return fail(QLZX_R_BAD_ARG, "qlzx_htree_index: null arg");
+    if (int r = check_workspace("qlzx_htree_index", workspace, workspace_bytes, qlzx_htree_index_workspace_size(height)))
+        return r;
+    const qlzx::HtgTree T{image, bytes, nullptr, g};
+    return launched("qlzx_htree_index", qlzx::launch_hti(T, leaf_first, totals, workspace, (hipStream_t)stream));
+}
+
+size_t qlzx_htree_get_workspace_size(uint32_t n) { return qlzx::htg_ws_layout(n, nullptr, nullptr); }
+
+int qlzx_htree_get(const uint8_t *image, uint64_t bytes, const uint32_t *leaf_first, uint32_t depth, uint32_t height,
+                   const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len, const uint64_t *keyhash,
+                   uint32_t n, uint32_t flags, int32_t *status, uint32_t *chunk, uint32_t *offset, int32_t *ver,
+                   uint16_t *vhash, uint32_t *slot, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                   void *stream) {
+    if (n == 0) return QLZX_R_OK;
+    qlzx::HtGeo g;
+    if (int r = check_htg_tree("qlzx_htree_get", image, bytes, depth, height, &g)) return r;
+    // keyhash may be null: the default hash of the request's key, which the three key arrays then name
+    if (!leaf_first || (!keyhash && (!keys || !key_off || !key_len)) || !status || !chunk || !offset || !ver ||
+        !vhash || !slot || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_htree_get: null arg");
+    bool lane;
+    if (int r = htg_shape("qlzx_htree_get", flags, n, bytes, g, &lane)) return r;
+    if (int r = check_workspace("qlzx_htree_get", workspace, workspace_bytes, qlzx_htree_get_workspace_size(n))) return r;
+    const qlzx::HtgTree T{image, bytes, leaf_first, g};
+    const qlzx::HtgOut out{status, chunk, offset, ver, vhash, slot, nullptr};
+    return launched("qlzx_htree_get", qlzx::launch_htg(T, keys, key_off, key_len, keyhash, n, lane, out, workspace,
+                    totals, (hipStream_t)stream));
+}
+
+size_t qlzx_gc_liveness_workspace_size(uint32_t cap) { return qlzx::gl_ws_layout(cap, nullptr, nullptr); }
+
+int qlzx_gc_liveness(const uint8_t *data, uint64_t size, const uint64_t *rec_off, const uint32_t *result, uint32_t cap,
+                     uint32_t max_key, uint64_t body_max, uint32_t src_chunk, const uint8_t *image, uint64_t bytes,
+                     const uint32_t *leaf_first, uint32_t depth, uint32_t height, const uint64_t *keyhash,
+                     uint32_t flags, uint8_t *keep, int32_t *verdict, uint16_t *vhash, int32_t *tree_ver,
+                     uint32_t *slot, uint32_t *ask_idx, uint32_t *totals, void *workspace, size_t workspace_bytes,
+                     void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    qlzx::HtGeo g;
+    if (int r = check_htg_tree("qlzx_gc_liveness", image, bytes, depth, height, &g)) return r;
+    if ((!data && size) || !rec_off || !result || !leaf_first || !keep || !verdict || !vhash || !tree_ver || !slot ||
+        !ask_idx || !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_gc_liveness: null arg");
+    if (flags & ~(uint32_t)QLZX_GL_F_BEGIN_GT_0) return fail(QLZX_R_BAD_ARG, "qlzx_gc_liveness: unknown flag");
+    if ((uintptr_t)data & 15u) return fail(QLZX_R_BAD_ARG, "qlzx_gc_liveness: data is not 16-B aligned");
+    if (int r = check_chunk_size("qlzx_gc_liveness", size)) return r;
+    if (int r = check_workspace("qlzx_gc_liveness", workspace, workspace_bytes, qlzx_gc_liveness_workspace_size(cap)))
+        return r;
+    const qlzx::GlIn in{data, size, rec_off, result, cap, max_key, body_max};
+    const qlzx::HtgTree T{image, bytes, leaf_first, g};
+    return launched("qlzx_gc_liveness", qlzx::launch_gl(in, src_chunk, T, keyhash, flags, qlzx::htg_lane_shape(cap, bytes, g),
+                    keep, verdict, vhash, tree_ver, slot, ask_idx, totals, workspace, (hipStream_t)stream));
+}
+
+size_t qlzx_htree_move_workspace_size(uint32_t cap) { return qlzx::htm_ws_layout(cap, nullptr, nullptr); }
+
+int qlzx_htree_move(uint8_t *image, uint64_t bytes, const uint32_t *leaf_first, uint32_t depth, uint32_t height,
+                    const uint32_t *result, uint32_t cap, const int32_t *verdict, const int32_t *gc_status,
+                    const uint32_t *slot, const uint32_t *new_chunk, const uint64_t *new_off,
+                    const uint32_t *dst_chunk_id, uint32_t max_chunks, uint32_t *totals, void *workspace,
+                    size_t workspace_bytes, void *stream) {
+    if (cap == 0) return QLZX_R_OK;
+    qlzx::HtGeo g;
+    if (int r = check_htg_tree("qlzx_htree_move", image, bytes, depth, height, &g)) return r;
+    if (!leaf_first || !result || !verdict || !gc_status || !slot || !new_chunk || !new_off || !dst_chunk_id ||
+        !totals)
+        return fail(QLZX_R_BAD_ARG, "qlzx_htree_move: null arg");
+    if (int r = check_workspace("qlzx_htree_move", workspace, workspace_bytes, qlzx_htree_move_workspace_size(cap)))
+        return r;
+    const qlzx::HtgTree T{image, bytes, leaf_first, g};
+    const qlzx::HtmIn in{result, cap, verdict, gc_status, slot, new_chunk, new_off, dst_chunk_id, max_chunks};
+    return launched("qlzx_htree_move", qlzx::launch_htm(T, image, in, totals, workspace, (hipStream_t)stream));
 }
 
 int qlzx_vhash_batch(const uint8_t *src, const uint64_t *off, const uint32_t *len, uint32_t n, uint16_t *out,

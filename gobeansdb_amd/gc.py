@@ -2,9 +2,11 @@
 
 Host mirror of the data movement of GCMgr.gc (store/gc.go:268-353) for one source
 chunk resident in device memory: the records the stream reader returns (their offsets
-come from qlzx_replay_index, gobeansdb_amd/replay.py) are filtered by the caller's
-liveness mask -- the HTree / hint / collision lookups that decide isNewest are out of
-scope -- and every kept record is appended to the destination in order, as
+come from qlzx_replay_index, gobeansdb_amd/replay.py) are filtered by a liveness mask
+-- liveness() below makes it on the device from the bucket's HTree image
+(store/gc.go:280-312, qlzx_gc_liveness); the collision table and the in-memory hint
+buffers that getCollisionGC consults stay the caller's, for the records liveness()
+lists in ask_idx -- and every kept record is appended to the destination in order, as
 dataChunk.AppendRecordGC -> WriteRecord.append (store/datachunk.go:56-79,
 store/datafile.go:307-330) does: header re-encoded with its CRC recomputed over
 header[4:24] ‖ key ‖ value (store/datafile.go:66-88), zero padding to 256 B, and a new
@@ -193,3 +195,53 @@ def rewrite(data: torch.Tensor, rec_off: torch.Tensor, keep: torch.Tensor, dst_h
         buf.view(torch.int32)[_dev.u64(local // 4, dev)] = got
         crc[sel] = _dev.readback(got)
     return GCResult(chunks, chunk, off, crc, int((crc != stored_crc).sum()))
+
+
+@dataclass
+class GCLiveness:
+    """liveness()'s result: one entry per record of rec_off, on the device; only totals is read back."""
+    keep: torch.Tensor       # uint8: 1 for a record GC rewrites; goes straight into rewrite_batch
+    verdict: torch.Tensor    # int32: _lib.GL_BAD / GL_NEWEST / GL_OTHER_POS / GL_NOT_IN_TREE
+    vhash: torch.Tensor      # int16 (u16 bits): the tree's value hash of a found key
+    tree_ver: torch.Tensor   # int32: the tree's version of a found key (isDeleted = tree_ver < 0)
+    slot: torch.Tensor       # int32 (u32 bits): the key's item in the image, HTG_NO_SLOT when not found
+    ask_idx: torch.Tensor    # int32 [totals[GL_N_OTHER_POS]]: the OTHER_POS records, ascending
+    totals: np.ndarray       # uint32 [8]: records, NEWEST, OTHER_POS, of those deleted, NOT_IN_TREE, of those kept, BAD, keep
+
+
+@on_stream
+def liveness(data: torch.Tensor, rec_off: torch.Tensor, tree, src_chunk: int, begin_gt_0: bool = False,
+             keyhash: torch.Tensor | None = None, stream=None) -> GCLiveness:
+    """GC's verdict per record of the chunk `data` (store/gc.go:280-312, qlzx_gc_liveness) against
+    `tree` (an htree.HTreeImage): a record is kept when the tree finds its key at
+    (src_chunk, its offset), or when the key is not in the tree, begin_gt_0 (gc.Begin > 0) and the
+    record is a delete.  Records whose key the tree finds elsewhere are listed in ask_idx, for a
+    caller with a collision table to resolve; without one their keep = 0 stands.  keyhash
+    (int64, one per record) replaces the default hash of the records' keys."""
+    L = _lib.lib()
+    dev = data.device
+    size, n = int(data.numel()), int(rec_off.numel())
+    cap = max(n, 1)
+    rec_off = _dev.u64(rec_off, dev)
+    if keyhash is not None:
+        if keyhash.numel() != n:
+            raise ValueError("keyhash: one per record")
+        keyhash = _dev.u64(keyhash, dev)
+    result = torch.tensor([n, 0, 0, 0], dtype=torch.int32, device=dev)
+    keep = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    verdict, tree_ver, slot, ask_idx = (torch.zeros(cap, dtype=torch.int32, device=dev) for _ in range(4))
+    vhash = torch.zeros(cap, dtype=torch.int16, device=dev)
+    totals = torch.zeros(8, dtype=torch.int32, device=dev)
+    if n:
+        ws_bytes = L.qlzx_gc_liveness_workspace_size(cap)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.qlzx_gc_liveness(ptr(data), size, rec_off.data_ptr(), result.data_ptr(), cap, MAX_KEY_LEN,
+                                      BODY_MAX, src_chunk, ptr(tree.file), int(tree.file.numel()),
+                                      tree.leaf_first.data_ptr(), tree.depth, tree.height, ptr(keyhash),
+                                      _lib.GL_F_BEGIN_GT_0 if begin_gt_0 else 0, keep.data_ptr(),
+                                      verdict.data_ptr(), vhash.data_ptr(), tree_ver.data_ptr(), slot.data_ptr(),
+                                      ask_idx.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes,
+                                      batch._stream()), "qlzx_gc_liveness")
+    t = _dev.readback(totals)                              # the read-back
+    return GCLiveness(keep[:n], verdict[:n], vhash[:n], tree_ver[:n], slot[:n],
+                      ask_idx[:int(t[_lib.GL_N_OTHER_POS])], t)

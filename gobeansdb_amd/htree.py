@@ -10,8 +10,13 @@ qlzx_htree_write, include/qlzx_htree.h, csrc/qlzx_htree.hip); the host reads bac
 HTreeBuilt.list_dir answers the @path listing (HTree.ListDir, store/htree.go:361-436) on the host,
 over the few nodes or the leaf range it reads back.
 
-HTree.get / set on a live tree, htree.load and the store-level tree over the bucket roots stay
-out of scope; the caller owns the files' bytes.
+The built tree is queried as its .hash image plus leaf_first (HTreeImage; include/qlzx_htree_get.h,
+csrc/qlzx_htree_get.hip): load_image() is HTree.load of an uploaded file, HTreeBuilt.image() the
+same of a tree just built, get() a batched HTree.get (store/htree.go:313-330) and move()
+UpdateHtreePos (store/gc.go:85-94) for the records gc.liveness() -> gc.rewrite_batch() moved.
+
+HTree.set / remove of new writes on a live image (they grow leaves) and the store-level tree over
+the bucket roots stay out of scope; the caller owns the files' bytes.
 """
 from __future__ import annotations
 
@@ -53,6 +58,12 @@ class HTreeBuilt:
     slot_src: torch.Tensor | None = field(default=None, repr=False)
     slot_chunk: torch.Tensor | None = field(default=None, repr=False)
     hints: torch.Tensor | None = field(default=None, repr=False)
+
+    def image(self) -> "HTreeImage":
+        """The tree as get() / gc.liveness() / move() take it: the build already has leaf_first."""
+        if self.file.numel() == 0:
+            raise ValueError("htree: image() needs the file (build with write=True)")
+        return HTreeImage(self.file, self.leaf_first, self.n_slots, self.depth, self.height)
 
     def node(self, level: int, offset: int) -> tuple[int, int]:
         """(count, hash) of one node: a read-back."""
@@ -173,3 +184,116 @@ def build(files, chunk_ids, depth: int, height: int = 3, write: bool = True,
         return build_packed(torch.empty(0, dtype=torch.uint8, device=dev), [], [], [], depth, height, write)
     hints, offs, lens = hint._pack(files)
     return build_packed(hints, offs, lens, chunk_ids, depth, height, write, None, workspace)
+
+
+# ---- queries over a built tree (include/qlzx_htree_get.h) ----
+@dataclass
+class HTreeImage:
+    """A tree as the query calls take it: the .hash image and the exclusive scan of its leaves'
+    item counts, both on the device."""
+    file: torch.Tensor        # uint8 (device): the .hash file's bytes; move() rewrites positions in place
+    leaf_first: torch.Tensor  # int32 [nleaf + 1] (device)
+    n_items: int
+    depth: int
+    height: int
+
+
+@dataclass
+class HTreeGet:
+    status: torch.Tensor     # int32 [n] (device): _lib.HTG_MISS / HTG_FOUND
+    chunk: torch.Tensor      # int32 [n] (u32 bits): the chunk stored in the item
+    offset: torch.Tensor     # int32 [n] (u32 bits): the record's offset in its chunk
+    ver: torch.Tensor        # int32 [n]: negative for an item that records a delete
+    vhash: torch.Tensor      # int16 [n] (u16 bits)
+    slot: torch.Tensor       # int32 [n] (u32 bits): the item's index in the image, HTG_NO_SLOT for a miss
+    totals: tuple            # (found, miss), read back once
+
+    def __iter__(self):
+        return iter((self.status, self.chunk, self.offset, self.ver, self.vhash, self.slot, self.totals))
+
+
+@on_stream
+def load_image(file: torch.Tensor, depth: int, height: int = 3, workspace: batch.Workspace | None = None,
+               stream=None) -> HTreeImage:
+    """HTree.load (store/htree.go:107-144) of a .hash file in device memory: its leaf_first
+    (qlzx_htree_index).  Raises QlzxError naming the leaf where the reference's reader fails, or
+    whose length is no whole number of items (HTG_BAD_FILE).  totals[4] is read back."""
+    L = _lib.lib()
+    _, nleaf = geometry(depth, height)
+    dev = file.device
+    if file.data_ptr() % 16 or not file.is_contiguous():     # the calls load aligned dwords from the image
+        file = file.clone(memory_format=torch.contiguous_format)
+    leaf_first = torch.empty(nleaf + 1, dtype=torch.int32, device=dev)
+    totals = torch.zeros(4, dtype=torch.int32, device=dev)
+    ws_bytes = L.qlzx_htree_index_workspace_size(height)
+    ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
+    _lib.check(L.qlzx_htree_index(ptr(file), int(file.numel()), depth, height, leaf_first.data_ptr(),
+                                  totals.data_ptr(), ws.data_ptr(), ws_bytes, batch._stream()), "qlzx_htree_index")
+    t = _dev.readback(totals)                       # the read-back
+    if int(t[_lib.HTG_STATUS]) != _lib.HTG_OK:
+        raise _lib.QlzxError(f"qlzx_htree_index: HTG_BAD_FILE, leaf {int(t[_lib.HTG_STATUS_LEAF])}")
+    return HTreeImage(file, leaf_first, int(t[_lib.HTG_ITEMS]), depth, height)
+
+
+@on_stream
+def get(tree: HTreeImage, keys: batch.BlockBatch | None = None, keyhash: torch.Tensor | None = None,
+        workspace: batch.Workspace | None = None, stream=None, _shape: str | None = None) -> HTreeGet:
+    """HTree.get of every key (qlzx_htree_get): the lowest item of the key's leaf whose stored low
+    bytes equal the keyhash's.  keyhash (int64 [n]) replaces the default hash of `keys`, which may
+    then be None.  The results stay on the device; the two totals are read back.  `offset` widened
+    to int64 is what replay.read_records takes.  _shape ("lane" / "wave") names the kernel, for
+    tests and sweeps: the outputs do not depend on it."""
+    L = _lib.lib()
+    dev = tree.file.device
+    if keyhash is not None:
+        keyhash = _dev.u64(keyhash, dev)
+        n = int(keyhash.numel())
+        if keys is not None and keys.n != n:
+            raise ValueError("keyhash: one per key")
+    elif keys is None:
+        raise ValueError("htree.get: keys or keyhash")
+    else:
+        n = keys.n
+    status, chunk, offset, ver, slot = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(5))
+    vhash = torch.zeros(n, dtype=torch.int16, device=dev)
+    if n == 0:
+        return HTreeGet(status, chunk, offset, ver, vhash, slot, (0, 0))
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
+    ws_bytes = L.qlzx_htree_get_workspace_size(n)
+    ws = (workspace or batch.Workspace(dev)).get(ws_bytes)
+    flags = {None: 0, "lane": _lib.HTG_F_LANE, "wave": _lib.HTG_F_WAVE}[_shape]
+    kd, ko, kl = (ptr(keys.data), ptr(keys.off), ptr(keys.length)) if keys is not None else (None, None, None)
+    _lib.check(L.qlzx_htree_get(ptr(tree.file), int(tree.file.numel()), tree.leaf_first.data_ptr(), tree.depth,
+                                tree.height, kd, ko, kl, ptr(keyhash), n, flags, status.data_ptr(),
+                                chunk.data_ptr(), offset.data_ptr(), ver.data_ptr(), vhash.data_ptr(),
+                                slot.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes, batch._stream()),
+               "qlzx_htree_get")
+    t = _dev.readback(totals)                       # the read-back
+    return HTreeGet(status, chunk, offset, ver, vhash, slot, (int(t[0]), int(t[1])))
+
+
+@on_stream
+def move(tree: HTreeImage, liveness, gc_batch, dst_chunk_ids, stream=None) -> tuple[int, int]:
+    """UpdateHtreePos for a whole chunk (qlzx_htree_move): every record that gc.liveness() called
+    NEWEST and gc.rewrite_batch() wrote gets its new position into its item of tree.file, in
+    place.  dst_chunk_ids[c] is the real chunk id of gc_batch's destination chunk c.  Returns
+    (moved, skipped), read back."""
+    L = _lib.lib()
+    dev = tree.file.device
+    n = int(liveness.verdict.numel())
+    if int(gc_batch.status.numel()) != n:
+        raise ValueError("move: liveness and gc_batch are of the same records")
+    ids = _dev.u32(list(dst_chunk_ids), dev)
+    if n == 0 or ids.numel() == 0:
+        return 0, 0
+    result = torch.tensor([n, 0, 0, 0], dtype=torch.int32, device=dev)
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
+    ws_bytes = L.qlzx_htree_move_workspace_size(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(L.qlzx_htree_move(ptr(tree.file), int(tree.file.numel()), tree.leaf_first.data_ptr(), tree.depth,
+                                 tree.height, result.data_ptr(), n, liveness.verdict.data_ptr(),
+                                 gc_batch.status.data_ptr(), liveness.slot.data_ptr(), gc_batch.new_chunk.data_ptr(),
+                                 gc_batch.new_off.data_ptr(), ids.data_ptr(), int(ids.numel()), totals.data_ptr(),
+                                 ws.data_ptr(), ws_bytes, batch._stream()), "qlzx_htree_move")
+    t = _dev.readback(totals)                       # the read-back
+    return int(t[_lib.HTM_MOVED]), int(t[_lib.HTM_SKIPPED])
